@@ -1,8 +1,16 @@
 """Flagship benchmark: SPADE/GauGAN training throughput, 256x512, bf16.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line; it measures
+nothing else. ``--full`` is where measurements beyond the headline figure belong (there are
+none at present: the profiling options below are each asked for by name). ``--dump-outputs
+DIR`` writes what the last timed step left its caller (see ``_dump_outputs``), so that two
+builds can be compared output for output: weights, data and noise are seeded, and that last
+step starts from the seeded state again (see ``_Seeded``), so the same arguments give it the
+same inputs in every run.
 
 Metric (BASELINE.json): whole-node images/s for SPADE 256x512 — one "step" is
 one full training iteration of the reference SPADE trainer: D update (G
@@ -40,6 +48,14 @@ def parse():
     p.add_argument('--config', default=os.path.join(HERE, 'configs', 'bench',
                                                      'spade_256x512_synthetic.yaml'))
     p.add_argument('--batch', type=int, default=None, help='per-GPU batch (default: config)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last step computed (losses, and a '
+                        'fixed seeded sample of the updated G / D state) as DIR/<name>.npy; '
+                        'that step starts from the seeded initial state, put back with the '
+                        'clock stopped')
+    p.add_argument('--full', action='store_true',
+                   help='also run every measurement and check beyond the headline figure (none '
+                        'at present: a plain run already does only what its result line needs)')
     p.add_argument('--eager', action='store_true',
                    help='self-baseline: PyTorch reference ops instead of the HIP kernels '
                         '(implies --no-graph)')
@@ -183,6 +199,9 @@ def main():
         data = trainer.start_of_iteration(data, it)
         run_step(data)
 
+    # --dump-outputs: the last timed step starts from the seeded state held here (see _Seeded)
+    seeded = _Seeded(trainer, src, device) if args.dump_outputs else None
+
     for it in range(args.warmup):
         step(it)
         if rank == 0:
@@ -278,12 +297,19 @@ def main():
         except Exception:  # noqa: BLE001
             pass
     t0 = time.perf_counter()
+    paused = 0.0
     for it in range(args.steps):
+        if seeded is not None and it == args.steps - 1:
+            barrier()  # the clock stops while the seeded state is put back
+            t1 = time.perf_counter()
+            seeded.restore()
+            barrier()
+            paused = time.perf_counter() - t1
         step(args.warmup + it)
         if rank == 0 and args.verbose:
             print('[bench] step {} queued'.format(it), flush=True)
     barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
     t = torch.tensor([elapsed], device=device if args.backend == 'nccl' and on_gpu else 'cpu',
                      dtype=torch.float64)
     if world > 1:
@@ -310,6 +336,8 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * bs * args.steps / elapsed
     mem_gb = torch.cuda.max_memory_allocated(device) / 2 ** 30 if on_gpu else 0.0
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(trainer, args.dump_outputs)
     sys.stdout = real_stdout
     if rank == 0:
         out = {
@@ -364,6 +392,106 @@ def _last_losses(trainer):
             if torch.is_tensor(v) and v.numel() == 1:
                 out['%s/%s' % (tag, k)] = round(float(v), 5)
     return out
+
+
+class _Seeded(object):
+    """The state a step starts from, taken right after the seeded set-up: G (with its averaged
+    copy) and D parameters and buffers, the random generators, the batch source's position.
+    ``restore()`` puts it back in place (a captured step keeps its pointers), zeroes the Adam
+    moments and rewinds the optimizers' step counters.
+
+    ``--dump-outputs`` restores it before the last timed step, with the clock stopped. Without
+    that the dumped step would start from wherever the earlier steps led, and that is no fixed
+    point: the default kernels accumulate with atomics, Adam's first steps turn a last-bit
+    difference of a small gradient into a +-lr difference of its weight, and GAN training
+    grows it from there. Measured on one MI355X, same build and arguments, relative L2
+    distance of the sampled G state between two runs: 9e-6 after 1 step, 4e-3 after 3, 8e-2
+    after 7, 5e-1 after 25 (the G loss 11.05 against 9.14). From the restored state two runs
+    of --steps 20 --warmup 5 (graph replays) agree as after 1 step, with each other and with
+    an eager first step: every loss bitwise, the sampled state to 9e-6 (at most 2 lr per
+    weight). So two builds can be compared at any --steps. The stop costs the timed window one
+    extra synchronisation: 72.1-72.3 ms per step against 71.9-72.0 without the option."""
+
+    def __init__(self, trainer, src, device):
+        import copy
+        import torch
+        self.trainer, self.src, self.device = trainer, src, device
+        self.nets = [(net, copy.deepcopy(net.state_dict()))
+                     for net in (trainer.net_G, trainer.net_D) if net is not None]
+        self.src_step = src.step
+        self.cpu_rng = torch.get_rng_state()
+        self.gpu_rng = torch.cuda.get_rng_state(device) if device.type == 'cuda' else None
+
+    def restore(self):
+        import torch
+        with torch.no_grad():
+            for net, state in self.nets:
+                net.load_state_dict(state)
+            for opt in (self.trainer.opt_G, self.trainer.opt_D):
+                if opt is None:
+                    continue
+                sd = opt.state_dict()
+                moments = [t for s in sd['state'].values() for t in s.values()
+                           if torch.is_tensor(t)]
+                where = [t.data_ptr() for t in moments]
+                for t in moments:
+                    t.zero_()
+                for g in sd['param_groups']:
+                    if 'step' in g:
+                        g['step'] = 0
+                opt.load_state_dict(sd)  # (FusedAdam: also rewinds its device step counter)
+                now = [t.data_ptr() for s in opt.state_dict()['state'].values()
+                       for t in s.values() if torch.is_tensor(t)]
+                assert now == where, 'optimizer state moved: a captured step would not see it'
+        self.src.step = self.src_step
+        torch.set_rng_state(self.cpu_rng)
+        if self.gpu_rng is not None:
+            torch.cuda.set_rng_state(self.gpu_rng, self.device)
+
+
+DUMP_BYTES_PER_NET = 24 << 20  # two networks: 48 MB of float32 at the most
+
+
+def _state_sample(net, gen):
+    """A fixed sample of every floating-point tensor of ``net.state_dict()`` (parameters, the
+    averaged generator, BatchNorm statistics, spectral-norm u / v), in key order, as one
+    float32 vector: tensors up to the per-tensor cap whole, larger ones at indices drawn from
+    ``gen`` (logical element order, so the memory format of a tensor does not matter)."""
+    import torch
+    state = [(k, v) for k, v in sorted(net.state_dict().items())
+             if torch.is_tensor(v) and v.is_floating_point() and v.numel() > 0]
+    cap = max(16, min(4096, DUMP_BYTES_PER_NET // 4 // max(1, len(state))))
+    parts = []
+    for _, v in state:
+        flat = v.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = torch.randint(0, flat.numel(), (cap,), generator=gen)
+            flat = flat.index_select(0, idx.to(flat.device))
+        parts.append(flat.float().cpu())
+    return torch.cat(parts).numpy()[:DUMP_BYTES_PER_NET // 4]
+
+
+def _dump_outputs(trainer, out_dir):
+    """What the last timed step handed its caller, as ``out_dir/<name>.npy``: the D and G
+    losses it left in ``trainer.dis_losses`` / ``trainer.gen_losses`` (float64, in sorted key
+    order) and the state it updated, G with its averaged copy and D (float32, a fixed seeded
+    sample per tensor: see ``_state_sample``)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, src in (('gen_losses', trainer.gen_losses), ('dis_losses', trainer.dis_losses)):
+        keys = sorted(k for k, v in src.items() if torch.is_tensor(v) and v.numel() == 1)
+        arrays[name] = np.array([float(src[k]) for k in keys], dtype=np.float64)
+    gen = torch.Generator().manual_seed(20240229)
+    for name, net in (('net_G_state', trainer.net_G), ('net_D_state', trainer.net_D)):
+        if net is not None:
+            arrays[name] = _state_sample(net, gen)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    print('[bench] wrote %s to %s (%.1f MB)' % (
+        ', '.join(sorted(arrays)), out_dir, sum(a.nbytes for a in arrays.values()) / 1e6),
+        flush=True)
 
 
 def _replicas_in_sync(trainer, world, device):
