@@ -120,7 +120,7 @@ at::Tensor conv2d_mfma(const at::Tensor& x, const at::Tensor& w, const c10::opti
                        int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
                        double slope, int64_t nb, int64_t ncv,
                        const c10::optional<at::Tensor>& residual,
-                       const c10::optional<at::Tensor>& ascale);
+                       const c10::optional<at::Tensor>& ascale, int64_t pad_mode);
 at::Tensor conv2d_dgrad_mfma(const at::Tensor& dy, const at::Tensor& w, int64_t ph, int64_t pw,
                              int64_t ncv, const c10::optional<at::Tensor>& ascale);
 at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
@@ -128,9 +128,10 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
                              int64_t dw, int64_t out_cout, int64_t out_cin, bool out_bf16,
                              int64_t nb, int64_t variant,
                              const c10::optional<std::vector<at::Tensor>>& sn,
-                             const c10::optional<at::Tensor>& dst);
+                             const c10::optional<at::Tensor>& dst, int64_t pad_mode);
 bool conv2d_wgrad_v2_eligible(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
-                              int64_t sh, int64_t sw, int64_t dh, int64_t dw, int64_t nb);
+                              int64_t sh, int64_t sw, int64_t dh, int64_t dw, int64_t nb,
+                              int64_t pad_mode);
 // conv_tapsplit.hip
 at::Tensor conv_tap_sum(const at::Tensor& z, const c10::optional<at::Tensor>& bias, int64_t Cout,
                         int64_t KH, int64_t KW, int64_t ph, int64_t pw, int64_t dh, int64_t dw);
@@ -152,9 +153,12 @@ at::Tensor conv_weight_flip_t(const at::Tensor& w, int64_t s, int64_t qy, int64_
 std::vector<at::Tensor> conv_weight_phase_flip(const at::Tensor& w, int64_t s);
 void lds_poison(int64_t blocks);
 at::Tensor im2col_pack(const at::Tensor& x, int64_t KH, int64_t KW, int64_t sh, int64_t sw,
-                       int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t Kp);
+                       int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t Kp,
+                       int64_t pad_mode);
 
 int64_t conv_last_variant();
+bool conv_last_rw_narrow();
+int64_t wgrad_last_kernel();
 at::Tensor pad_nhwc_fwd(const at::Tensor& x, int64_t pl, int64_t pr, int64_t pt, int64_t pb,
                         int64_t mode);
 at::Tensor pad_nhwc_bwd(const at::Tensor& dy, int64_t H, int64_t W, int64_t pl, int64_t pr,
@@ -207,7 +211,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_mfma", &iamd::conv2d_mfma, "MFMA implicit-GEMM NHWC conv + bias + act (k10)",
         py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("sh"), py::arg("sw"), py::arg("ph"),
         py::arg("pw"), py::arg("dh"), py::arg("dw"), py::arg("slope"), py::arg("nb") = 1,
-        py::arg("ncv") = -1, py::arg("residual") = py::none(), py::arg("ascale") = py::none());
+        py::arg("ncv") = -1, py::arg("residual") = py::none(), py::arg("ascale") = py::none(),
+        py::arg("pad_mode") = 0);
   m.def("conv2d_dgrad_mfma", &iamd::conv2d_dgrad_mfma,
         "stride-1 conv data gradient from the forward weight (k10 v4 transposed-weight path)",
         py::arg("dy"), py::arg("w"), py::arg("ph"), py::arg("pw"), py::arg("ncv") = -1,
@@ -219,11 +224,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dy"), py::arg("x"), py::arg("KH"), py::arg("KW"), py::arg("sh"), py::arg("sw"),
         py::arg("ph"), py::arg("pw"), py::arg("dh"), py::arg("dw"), py::arg("out_cout") = -1,
         py::arg("out_cin") = -1, py::arg("out_bf16") = false, py::arg("nb") = 1,
-        py::arg("variant") = 0, py::arg("sn") = py::none(), py::arg("dst") = py::none());
+        py::arg("variant") = 0, py::arg("sn") = py::none(), py::arg("dst") = py::none(),
+        py::arg("pad_mode") = 0);
   m.def("conv2d_wgrad_v2_eligible", &iamd::conv2d_wgrad_v2_eligible,
         "whether the k11 v2 (one wave per SIMD) kernel can run this weight gradient",
         py::arg("dy"), py::arg("x"), py::arg("KH"), py::arg("KW"), py::arg("sh"), py::arg("sw"),
-        py::arg("dh"), py::arg("dw"), py::arg("nb") = 1);
+        py::arg("dh"), py::arg("dw"), py::arg("nb") = 1, py::arg("pad_mode") = 0);
   m.def("channel_softmax_fwd", &iamd::channel_softmax_fwd,
         "softmax over the channels of a channels-last bf16 tensor (k15)");
   m.def("channel_softmax_bwd", &iamd::channel_softmax_bwd, "k15 backward: y * (dy - sum(dy y))");
@@ -251,10 +257,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flipped, in/out-transposed channels-last conv weight (dgrad-as-conv); s/qy/qx select "
         "the taps of one stride-s phase; nb per-sample weights", py::arg("w"), py::arg("s") = 1,
         py::arg("qy") = 0, py::arg("qx") = 0, py::arg("nb") = 1);
+  m.def("conv_last_rw_narrow", &iamd::conv_last_rw_narrow,
+        "the last row-window k10 launch on this thread took the narrow (128-row) variant");
+  m.def("wgrad_last_kernel", &iamd::wgrad_last_kernel,
+        "k11 kernel of the last conv2d_wgrad_mfma launch on this thread (0 one-tap generic, "
+        "1 one-tap ROWS, 2 multi-tap, 3 v2)");
   m.def("conv_last_variant", &iamd::conv_last_variant,
         "k10 tile of the last conv2d_mfma launch on this thread (1-5, 6 = row-window)");
   m.def("im2col_pack", &iamd::im2col_pack,
-        "tap-packed [M][Kp] operand of a thin-input (Cin <= 16) conv (bf16, channels-last)");
+        "tap-packed [M][Kp] operand of a thin-input (Cin <= 16) conv (bf16, channels-last)",
+        py::arg("x"), py::arg("KH"), py::arg("KW"), py::arg("sh"), py::arg("sw"), py::arg("ph"),
+        py::arg("pw"), py::arg("dh"), py::arg("dw"), py::arg("Kp"), py::arg("pad_mode") = 0);
   m.def("lds_poison", &iamd::lds_poison,
         "test support: fill every CU's LDS with NaN bits (finds reads of never-written LDS)",
         py::arg("blocks") = 2048);

@@ -109,6 +109,20 @@ __device__ __forceinline__ void chan_merge(float& n_a, float& mean_a, float& m2_
 __device__ __forceinline__ float act_fwd(float y, float slope) { return y > 0.f ? y : y * slope; }
 __device__ __forceinline__ float act_grad(float y, float slope) { return y > 0.f ? 1.f : slope; }
 
+// Padding index map of the conv loaders (k10 / k11 / im2col_pack ``pmode``): source index of
+// coordinate i of an axis of n pixels. 1 = reflect (one reflection about the border pixel: the
+// hosts check pad < n), 2 = replicate (clamp); 0 = zeros, the identity (the loaders then send
+// out-of-image coordinates to an out-of-range buffer offset instead).
+__host__ __device__ __forceinline__ int pad_map(int i, int n, int pmode) {
+  if (pmode == 1) {
+    i = i < 0 ? -i : i;
+    i = i >= n ? 2 * (n - 1) - i : i;
+  } else if (pmode == 2) {
+    i = i < 0 ? 0 : (i >= n ? n - 1 : i);
+  }
+  return i;
+}
+
 inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
 
 // XCD-aware remap of a 1-D block index (MI355X: 8 XCDs, round-robin dispatch).

@@ -44,6 +44,12 @@ struct ConvArgs {
   // Wo); nseg = B * Ho * nct segments; P = LDS window rows per segment, Ph = rows of the
   // even-column half of a stride-2 window
   int SW = 0, nct = 1, nseg = 0, P = 0, Ph = 0;
+  // padding mode: 0 zeros, 1 reflect, 2 replicate (pad_map, common.h). Non-zero: the loader
+  // reads the mapped source pixel of every tap itself — the conv of F.pad(x, mode) at padding 0
+  // without the padded copy. The v1 / v4 / v5 / row-window loaders implement it (v2 / v3, the
+  // phases kernel, per-sample launches and the Cin = 32 pair mode do not: run_conv routes around
+  // them, the host entry refuses the rest).
+  int pmode = 0;
 };
 
 namespace {
@@ -148,6 +154,7 @@ conv_splitk_reduce(const float* __restrict__ part, const float* __restrict__ bia
 // filters, Cout = 64, Cin = 32, output rows of any width): conv_rw.hip. Launches and returns
 // true when the shape is eligible (IMAGINAIRE_AMD_CONV_RW != 0), else launches nothing.
 bool run_rw(ConvArgs& a, const at::Tensor& x, bool forced);
+extern thread_local bool g_last_rw_narrow;
 bool rw_eligible(const ConvArgs& a);
 // the narrow row-window variant is switched on for this shape (IMAGINAIRE_AMD_CONV_RW_SMALL=1)
 bool rw_small_pref(const ConvArgs& a);

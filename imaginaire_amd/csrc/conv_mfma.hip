@@ -37,7 +37,11 @@ namespace {
 // then MFMAs; 1 = same with s_setprio(1) around the MFMA cluster; 2 = all 64-k fragments read
 // up front, then 32 back-to-back MFMAs under s_setprio(1).
 // The v1 body: tile bid (already XCD-remapped) of split `split` of sample zb (of nz).
-template <int BM, int BN, bool HAS_BIAS, int VAR>
+// PM (a.pmode != 0: reflect / replicate padding read in place): every tap of a row m < M reads
+// a real pixel, so instead of the linear a_off + tap offset and the tap mask each row keeps its
+// (image base, ih0, iw0) and a tap's source is built from the pad_map'ed coordinates (stride
+// and dilation are explicit in them). Zero padding (PM = false) is the loader as it was.
+template <int BM, int BN, bool HAS_BIAS, int VAR, bool PM = false>
 __device__ __forceinline__ void conv_v1_impl(const ConvArgs& a, int bid, int split, int zb,
                                              int nz) {
   // The buffer-resource builtins have no host form; the host pass only needs the launch stub.
@@ -71,15 +75,23 @@ __device__ __forceinline__ void conv_v1_impl(const ConvArgs& a, int bid, int spl
   const int HoWo = a.Ho * a.Wo;
   int a_off[4];
   uint64_t a_tmask[4];  // bit (ky * KW + kx) set when that filter tap reads inside the image
+  int a_ih0[4], a_iw0[4];  // PM: a_off = b * H (-1: row past M), input coordinates of tap (0, 0)
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int m = m0 + lrow + RS * i;
-    a_off[i] = 0;
+    a_off[i] = PM ? -1 : 0;
     a_tmask[i] = 0;
+    a_ih0[i] = a_iw0[i] = 0;
     if (m < a.M) {
       const int b = m / HoWo, r = m - b * HoWo;
       const int oh = r / a.Wo, ow = r - oh * a.Wo;
       const int ih0 = oh * a.sh - a.ph, iw0 = ow * a.sw - a.pw;
+      if constexpr (PM) {
+        a_off[i] = b * a.H;
+        a_ih0[i] = ih0;
+        a_iw0[i] = iw0;
+        continue;
+      }
       a_off[i] = (((b * a.H + ih0) * a.W + iw0) * a.Cin + csw * 8) * 2;
       for (int ky = 0; ky < a.KH; ++ky) {
         if ((unsigned)(ih0 + ky * a.dh) >= (unsigned)a.H) continue;
@@ -112,8 +124,16 @@ __device__ __forceinline__ void conv_v1_impl(const ConvArgs& a, int bid, int spl
     char* Bs = As + kAbytes;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const bool ok = (a_tmask[i] >> ctap) & 1u;
-      const int voff = ok ? a_off[i] + ctoff : kOobOffset;
+      int voff;
+      if constexpr (PM) {
+        const int ih = pad_map(a_ih0[i] + cky * a.dh, a.H, a.pmode);
+        const int iw = pad_map(a_iw0[i] + ckx * a.dw, a.W, a.pmode);
+        voff = a_off[i] >= 0 ? (((a_off[i] + ih) * a.W + iw) * a.Cin + cc + csw * 8) * 2
+                             : kOobOffset;
+      } else {
+        const bool ok = (a_tmask[i] >> ctap) & 1u;
+        voff = ok ? a_off[i] + ctoff : kOobOffset;
+      }
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(As + i * kLoadBytes + wid * 1024),
                                                16, voff, 0, 0, 0);
     }
@@ -248,10 +268,10 @@ __device__ __forceinline__ void conv_v1_impl(const ConvArgs& a, int bid, int spl
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <int BM, int BN, bool HAS_BIAS, int VAR>
+template <int BM, int BN, bool HAS_BIAS, int VAR, bool PM = false>
 __global__ __launch_bounds__(BM * 2, BM == 128 ? 2 : 1) void conv_fwd_mfma(ConvArgs a) {
-  conv_v1_impl<BM, BN, HAS_BIAS, VAR>(a, xcd_remap(blockIdx.x, gridDim.x), blockIdx.y,
-                                      blockIdx.z, gridDim.z);
+  conv_v1_impl<BM, BN, HAS_BIAS, VAR, PM>(a, xcd_remap(blockIdx.x, gridDim.x), blockIdx.y,
+                                          blockIdx.z, gridDim.z);
 }
 
 // Up to four independent convs in one launch (blockIdx.z = conv): the s*s phase convolutions
@@ -749,7 +769,11 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v3(ConvArgs a) {
 // its barrier while that step's kk = 0 fragments are still in flight — without it every tap
 // step began with all 8 waves waiting on LDS reads (MFMA pipe busy 54-63%,
 // profiles/pmc_conv_v4_r3_mi355x.txt).
-template <int KW, bool HAS_BIAS, bool BT, bool PF>
+// PM (a.pmode != 0: reflect / replicate padding read in place): the window column of a lane is
+// pad_map'ed once into a_off (no column is out of the image) and the filter row of each outer
+// step is mapped per lane from the segment's ih0, which a_km then holds instead of the
+// row-validity mask (a_off = kOobOffset marks the rows past the last segment).
+template <int KW, bool HAS_BIAS, bool BT, bool PF, bool PM = false>
 __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int BM = 256, BN = 128;
@@ -786,14 +810,20 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4(ConvArgs a) {
   for (int r = 0; r < 5; ++r) {
     const int row = r * 64 + wid * 8 + dr;
     const int s = row / L, j = row - s * L;
-    a_off[r] = 0;
+    a_off[r] = PM ? kOobOffset : 0;
     a_km[r] = 0;
     if (s < R) {
       const int m = m0 + s * SW;                  // first output pixel of segment s
       const int b = m / HoWo, rr = m - b * HoWo;
       const int oh = rr / a.Wo, ow0 = rr - oh * a.Wo;
       const int ih0 = oh - a.ph, iw = ow0 - a.pw + j;
-      if ((unsigned)iw < (unsigned)a.W) {
+      if constexpr (PM) {
+        const int mw = pad_map(iw, a.W, a.pmode);
+        if ((unsigned)mw < (unsigned)a.W) {
+          a_off[r] = b * a.H * rowbytes + (mw * a.Cin + csw * 8) * 2;
+          a_km[r] = (uint32_t)ih0;
+        }
+      } else if ((unsigned)iw < (unsigned)a.W) {
         a_off[r] = (b * a.H + ih0) * rowbytes + (iw * a.Cin + csw * 8) * 2;
         for (int ky = 0; ky < a.KH; ++ky)
           a_km[r] |= (uint32_t)((unsigned)(ih0 + ky) < (unsigned)a.H) << ky;
@@ -830,6 +860,14 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4(ConvArgs a) {
     char* As = smem + buf * kAbytes;
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
+      if constexpr (PM) {
+        const int row = pad_map((int)a_km[r] + ky, a.H, a.pmode);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            xrs, (lds_ptr_t)(As + r * 8192 + wid * 1024), 16,
+            live && a_off[r] != kOobOffset ? a_off[r] + row * rowbytes + cc * 2 : kOobOffset,
+            0, 0, 0);
+        continue;
+      }
       const bool ok = live && ((a_km[r] >> (ky & 31)) & 1u);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           xrs, (lds_ptr_t)(As + r * 8192 + wid * 1024), 16, ok ? a_off[r] + koff : kOobOffset,
@@ -1063,7 +1101,7 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4(ConvArgs a) {
 // 256-pixel segment per block) or one add per fragment (SW = 32..128).
 // DMA order per tap step: weights of the next tap, then (first tap of a filter row) the next
 // window, so the wait at tap 1 (vmcnt(5)) retires only the weights; other taps vmcnt(0).
-template <int KW, bool HAS_BIAS, bool FULLROW>
+template <int KW, bool HAS_BIAS, bool FULLROW, bool PM = false>
 __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v5(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int BM = 256, BN = 256;
@@ -1106,15 +1144,18 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v5(ConvArgs a) {
     const int b = m0 / HoWo, rr = m0 - b * HoWo;
     const int oh = rr / a.Wo, ow0 = rr - oh * a.Wo;
     const int ih0 = oh - a.ph;
-    uint32_t km = 0;
-    for (int ky = 0; ky < a.KH; ++ky) km |= (uint32_t)((unsigned)(ih0 + ky) < (unsigned)a.H) << ky;
+    // (PM, as v4: a_km holds ih0, the columns are pad_map'ed, the filter row per outer step)
+    uint32_t km = PM ? (uint32_t)ih0 : 0;
+    if constexpr (!PM)
+      for (int ky = 0; ky < a.KH; ++ky)
+        km |= (uint32_t)((unsigned)(ih0 + ky) < (unsigned)a.H) << ky;
     a_km[0] = __builtin_amdgcn_readfirstlane(km);
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
       const int j = r * 64 + wid * 8 + dr;
-      const int iw = ow0 - a.pw + j;
+      const int iw = PM ? pad_map(ow0 - a.pw + j, a.W, a.pmode) : ow0 - a.pw + j;
       a_off[r] = (j < SW + KW - 1 && (unsigned)iw < (unsigned)a.W)
-                     ? (b * a.H + ih0) * rowbytes + (iw * a.Cin + csw * 8) * 2
+                     ? (b * a.H + (PM ? 0 : ih0)) * rowbytes + (iw * a.Cin + csw * 8) * 2
                      : kOobOffset;
     }
   } else {
@@ -1128,11 +1169,16 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v5(ConvArgs a) {
         const int m = m0 + s * SW;
         const int b = m / HoWo, rr = m - b * HoWo;
         const int oh = rr / a.Wo, ow0 = rr - oh * a.Wo;
-        const int ih0 = oh - a.ph, iw = ow0 - a.pw + j;
+        const int ih0 = oh - a.ph;
+        const int iw = PM ? pad_map(ow0 - a.pw + j, a.W, a.pmode) : ow0 - a.pw + j;
         if ((unsigned)iw < (unsigned)a.W) {
-          a_off[r] = (b * a.H + ih0) * rowbytes + (iw * a.Cin + csw * 8) * 2;
-          for (int ky = 0; ky < a.KH; ++ky)
-            a_km[r] |= (uint32_t)((unsigned)(ih0 + ky) < (unsigned)a.H) << ky;
+          a_off[r] = (b * a.H + (PM ? 0 : ih0)) * rowbytes + (iw * a.Cin + csw * 8) * 2;
+          if constexpr (PM) {
+            a_km[r] = (uint32_t)ih0;
+          } else {
+            for (int ky = 0; ky < a.KH; ++ky)
+              a_km[r] |= (uint32_t)((unsigned)(ih0 + ky) < (unsigned)a.H) << ky;
+          }
         }
       }
     }
@@ -1154,6 +1200,14 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v5(ConvArgs a) {
     char* As = smem + kAoff + buf * kAbytes;
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
+      if constexpr (PM) {
+        const int row = pad_map((int)a_km[FULLROW ? 0 : r] + ky, a.H, a.pmode);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            xrs, (lds_ptr_t)(As + r * 8192 + wid * 1024), 16,
+            live && a_off[r] != kOobOffset ? a_off[r] + row * rowbytes + cc * 2 : kOobOffset,
+            0, 0, 0);
+        continue;
+      }
       const uint32_t ok = live & (a_km[FULLROW ? 0 : r] >> (ky & 31));
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           xrs, (lds_ptr_t)(As + r * 8192 + wid * 1024), 16,
@@ -1340,6 +1394,13 @@ void run_v4(ConvArgs& a, const at::Tensor& x, bool bt) {
   auto launch = [&](auto kv, auto hbv, auto btv) {
     constexpr int K = decltype(kv)::value;
     constexpr bool HB = decltype(hbv)::value, BTV = decltype(btv)::value;
+    if constexpr (!BTV) {
+      if (a.pmode != 0) {  // (forward convs only; the prefetching schedule)
+        hipLaunchKernelGGL((conv_fwd_mfma_v4<K, HB, false, true, true>), grid4, dim3(512), 0,
+                           stream(), a);
+        return;
+      }
+    }
     if (pf && !BTV)  // (the BT kernels have no registers left for a second fragment set)
       hipLaunchKernelGGL((conv_fwd_mfma_v4<K, HB, BTV, !BTV>), grid4, dim3(512), 0, stream(), a);
     else
@@ -1408,7 +1469,10 @@ void run_v5(ConvArgs& a, const at::Tensor& x) {
   auto launch = [&](auto kv, auto hbv, auto fv) {
     constexpr int K = decltype(kv)::value;
     constexpr bool HB = decltype(hbv)::value, FR = decltype(fv)::value;
-    hipLaunchKernelGGL((conv_fwd_mfma_v5<K, HB, FR>), grid, dim3(512), 0, stream(), a);
+    if (a.pmode != 0)
+      hipLaunchKernelGGL((conv_fwd_mfma_v5<K, HB, FR, true>), grid, dim3(512), 0, stream(), a);
+    else
+      hipLaunchKernelGGL((conv_fwd_mfma_v5<K, HB, FR>), grid, dim3(512), 0, stream(), a);
   };
   auto by_full = [&](auto kv, auto hbv) {
     if (full) launch(kv, hbv, std::true_type());
@@ -1436,6 +1500,9 @@ void run_v5(ConvArgs& a, const at::Tensor& x) {
 // 6 = row-window): read by the per-call conv log (ops/conv.py) and the tests.
 thread_local int g_last_conv_variant = 0;
 int64_t conv_last_variant() { return g_last_conv_variant; }
+// set by run_rw: the last row-window launch on this thread took the narrow (128-row) variant
+thread_local bool g_last_rw_narrow = false;
+bool conv_last_rw_narrow() { return g_last_rw_narrow; }
 
 namespace {
 
@@ -1454,6 +1521,9 @@ void run_conv(ConvArgs& a, const at::Tensor& x) {
   int ver = 0;
   if (const char* e = std::getenv("IMAGINAIRE_AMD_CONV_V")) ver = std::atoi(e);
   if (a.nz > 1) ver = 1;  // batched (per-sample weight) launches: v1 only
+  // reflect / replicate padding read in place: the v1 / v4 / v5 / row-window loaders map it;
+  // a forced v2 / v3 runs v1, and the default routing never picks v3
+  if (a.pmode != 0 && (ver == 2 || ver == 3)) ver = 1;
   const bool v3_ok = bn128 && KH * KW <= 31;
   const int v3_bn = Cout % 256 == 0 ? 256 : 128;
   const int v3_bm = v3_bn == 256 ? 256 : 512;
@@ -1499,7 +1569,7 @@ void run_conv(ConvArgs& a, const at::Tensor& x) {
     v3 = v3_ok;
   } else if (ver == 2) {
     v2 = bn128 && KH * KW <= 32;
-  } else if (ver == 0 && v3_ok && v3_bn == 256) {
+  } else if (ver == 0 && v3_ok && v3_bn == 256 && a.pmode == 0) {
     // (the 512 x 128 variant measured 0.88-0.98x v1 on the 128-channel SPADE / dgrad shapes:
     // selectable with IMAGINAIRE_AMD_CONV_V=3 only)
     // only grids that fill the chip without split-K: with the incremental-cursor v1 the split
@@ -1547,6 +1617,11 @@ void run_conv(ConvArgs& a, const at::Tensor& x) {
     constexpr int BM = decltype(bmv)::value;
     constexpr int BN = decltype(bnv)::value;
     constexpr bool HB = decltype(hbv)::value;
+    if (a.pmode != 0) {  // (one schedule per tile: VAR 2 at BM 128, 0 at BM 256)
+      hipLaunchKernelGGL((conv_fwd_mfma<BM, BN, HB, BM == 128 ? 2 : 0, true>), grid,
+                         dim3(BM * 2), 0, stream(), a);
+      return;
+    }
     if constexpr (BM == 128) {
       if (var == 1)
         hipLaunchKernelGGL((conv_fwd_mfma<BM, BN, HB, 1>), grid, dim3(BM * 2), 0, stream(), a);
@@ -1609,7 +1684,7 @@ at::Tensor conv2d_mfma(const at::Tensor& x, const at::Tensor& w, const c10::opti
                        int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
                        double slope, int64_t nb, int64_t ncv,
                        const c10::optional<at::Tensor>& residual,
-                       const c10::optional<at::Tensor>& ascale) {
+                       const c10::optional<at::Tensor>& ascale, int64_t pad_mode) {
   IAMD_CHECK(x.is_cuda() && w.is_cuda(), "conv2d_mfma: CUDA tensors expected");
   IAMD_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
              "conv2d_mfma: bf16 operands expected");
@@ -1633,6 +1708,16 @@ at::Tensor conv2d_mfma(const at::Tensor& x, const at::Tensor& w, const c10::opti
                  (int64_t)B * Ho * Wo * Cout < (1ll << 31),
              "conv2d_mfma: tensor too large for 32-bit buffer offsets");
   IAMD_CHECK(KH * KW <= 64, "conv2d_mfma: filters with more than 64 taps are not supported");
+  // pad_mode 1 reflect / 2 replicate: the padding pixels are read from x by the loader (the
+  // conv of F.pad(x, mode) at padding 0). Single-weight launches with Cin % 64 == 0 (the
+  // row-window tile's Cin = 32 pair mode does not map padding); one reflection per axis.
+  IAMD_CHECK(pad_mode >= 0 && pad_mode <= 2, "conv2d_mfma: pad_mode must be 0 (zeros), 1 "
+             "(reflect) or 2 (replicate), got ", pad_mode);
+  IAMD_CHECK(pad_mode == 0 || (nb == 1 && Cin % kBK == 0),
+             "conv2d_mfma: pad_mode != 0 needs a single-weight conv (nb == 1) with Cin % 64 == 0");
+  IAMD_CHECK(pad_mode != 1 || (ph < H && pw < W),
+             "conv2d_mfma: reflect padding (", ph, ", ", pw, ") must be smaller than the input (",
+             H, ", ", W, ")");
   if (ncv < 0) ncv = Cout;
   IAMD_CHECK(ncv == Cout || (nb == 1 && ncv > 0 && ncv < Cout && ncv % 8 == 0),
              "conv2d_mfma: stored channels must be Cout, or a multiple of 8 below it (nb == 1)");
@@ -1676,10 +1761,10 @@ at::Tensor conv2d_mfma(const at::Tensor& x, const at::Tensor& w, const c10::opti
   }
   a.ascale = ascale_ptr(ascale, "conv2d_mfma");
   IAMD_CHECK(a.ascale == nullptr || nb == 1, "conv2d_mfma: ascale is for single-weight convs");
+  a.pmode = (int)pad_mode;
   run_conv(a, x);
   return y;
 }
-
 
 at::Tensor conv_weight_flip_t(const at::Tensor& w, int64_t s, int64_t qy, int64_t qx, int64_t nb);
 std::vector<at::Tensor> conv_weight_phase_flip(const at::Tensor& w, int64_t s);
@@ -1725,7 +1810,7 @@ at::Tensor conv2d_dgrad_mfma(const at::Tensor& dy, const at::Tensor& w, int64_t 
   if (!ok) {
     const at::Tensor wt = conv_weight_flip_t(w, 1, 0, 0, 1);
     return conv2d_mfma(dy, wt, c10::nullopt, 1, 1, tph, tpw, 1, 1, 1.0, 1, ncv, c10::nullopt,
-                       ascale);
+                       ascale, 0);
   }
   if (ncv < 0) ncv = N;
   IAMD_CHECK(ncv == N || (ncv > 0 && ncv < N && ncv % 8 == 0),

@@ -65,7 +65,11 @@ __device__ __forceinline__ int rw_tapoff(int kx, int Ph) {
 // BMT / NR: block rows (256 | 128) and window DMA rounds (5 | 3). The narrow variant (stride 1,
 // BN 64, BMT 128, NR 3: 72 KB of LDS) runs two blocks per CU, so one block's loads overlap the
 // other's epilogue on the short-K convs (3x3 over 64 channels: 9 tap steps per block).
-template <int S, int KW, int BN, bool PAIR, int BMT, int NR>
+// PM (a.pmode != 0, not with PAIR): reflect / replicate padding read in place. The window column
+// of every lane is pad_map'ed once (no column is out of the image), and the filter row — one
+// per segment, so wave-uniform per DMA round — is mapped per outer step: a_km then holds the
+// round's ih0 instead of the row-validity mask.
+template <int S, int KW, int BN, bool PAIR, int BMT, int NR, bool PM = false>
 __global__ __launch_bounds__(512, (BMT == 128 && S == 1) ? 2 : 1) void conv_fwd_rw(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int BM = BMT;
@@ -117,7 +121,12 @@ __global__ __launch_bounds__(512, (BMT == 128 && S == 1) ? 2 : 1) void conv_fwd_
       const int c0 = S * ct * SW - a.pw;
       const int ih0 = oh * S - a.ph;
       uint32_t km = 0;
-      for (int ky = 0; ky < a.KH; ++ky) km |= (uint32_t)((unsigned)(ih0 + ky) < (unsigned)a.H) << ky;
+      if constexpr (PM) {
+        km = (uint32_t)ih0;
+      } else {
+        for (int ky = 0; ky < a.KH; ++ky)
+          km |= (uint32_t)((unsigned)(ih0 + ky) < (unsigned)a.H) << ky;
+      }
       a_km[r] = km;
       int iw;
       if constexpr (DEINT) {
@@ -128,8 +137,10 @@ __global__ __launch_bounds__(512, (BMT == 128 && S == 1) ? 2 : 1) void conv_fwd_
       } else {
         iw = c0 + j;
       }
+      if constexpr (PM) iw = pad_map(iw, a.W, a.pmode);
+      // (PM: window rows past the columns the taps read may map outside; they feed masked pixels)
       if ((unsigned)iw < (unsigned)a.W)
-        a_off[r] = (uint32_t)(((b * a.H + ih0) * a.W + iw) * a.Cin * 2 +
+        a_off[r] = (uint32_t)(((b * a.H + (PM ? 0 : ih0)) * a.W + iw) * a.Cin * 2 +
                               (PAIR ? (csw & 3) : csw) * 16);
     }
   }
@@ -165,6 +176,14 @@ __global__ __launch_bounds__(512, (BMT == 128 && S == 1) ? 2 : 1) void conv_fwd_
     char* As = smem + buf * kAbytes;
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
+      if constexpr (PM) {
+        const int row = pad_map((int)a_km[r] + ky, a.H, a.pmode);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            xrs, (lds_ptr_t)(As + r * 8192 + wid * 1024), 16,
+            live && a_off[r] != (uint32_t)kOobOffset
+                ? (int)(a_off[r] + (uint32_t)(row * rowbytes + cc * 2)) : kOobOffset, 0, 0, 0);
+        continue;
+      }
       const bool ok = live && ((a_km[r] >> (ky & 31)) & 1u);
       // (an out-of-image column keeps its out-of-range offset: kOobOffset + koff < 2^32)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
@@ -365,6 +384,7 @@ int pow2ceil(int v) {
 bool rw_plan(ConvArgs& a, double min_eff = 0.0, int bm = 0, int nr = kNR, bool any_sw = true) {
   if (a.nz != 1 || a.dh != 1 || a.dw != 1 || a.sh != a.sw || (a.sh != 1 && a.sh != 2))
     return false;
+  if (a.pmode != 0 && a.Cin == 32) return false;  // (the pair mode does not map padding)
   if (a.Cout % 64 != 0 || a.KH > 31 || a.KH < 1 || a.KW < 1) return false;
   const bool pair = a.Cin == 32;
   if (!pair && a.Cin % kBK != 0) return false;
@@ -426,6 +446,13 @@ bool rw_plan(ConvArgs& a, double min_eff = 0.0, int bm = 0, int nr = kNR, bool a
 
 template <int S, int KW, int BN, bool PAIR, int BMT = (S == 1 ? 256 : 128), int NR = kNR>
 void rw_launch(const ConvArgs& a, dim3 grid) {
+  if constexpr (!PAIR) {
+    if (a.pmode != 0) {
+      hipLaunchKernelGGL((conv_fwd_rw<S, KW, BN, PAIR, BMT, NR, true>), grid, dim3(512), 0,
+                         stream(), a);
+      return;
+    }
+  }
   hipLaunchKernelGGL((conv_fwd_rw<S, KW, BN, PAIR, BMT, NR>), grid, dim3(512), 0, stream(), a);
 }
 
@@ -521,6 +548,7 @@ bool run_rw(ConvArgs& a, const at::Tensor& x, bool forced) {
   // 0.92-0.93x v1, profiles/conv_rw_small_probe_r6_mi355x.txt)
   bool small = rw_small_pick(a) && rw_plan(a, forced ? 0.0 : 0.85, 128, 3, forced);
   if (!small && !rw_plan(a, forced ? 0.0 : 0.85, 0, kNR, forced)) return false;
+  g_last_rw_narrow = small;
   const int BM = small ? 128 : (a.sh == 1 ? 256 : 128);
   const int R = BM / a.SW;
   const int BN = a.Cout % 128 == 0 ? 128 : 64;

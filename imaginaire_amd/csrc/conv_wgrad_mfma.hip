@@ -60,6 +60,10 @@ struct WgradArgs {
   const __hip_bfloat16* wsn = nullptr;
   float* dotp = nullptr;
   int wsn_cout = 0, wsn_cin = 0;
+  // padding mode: 0 zeros, 1 reflect, 2 replicate (pad_map, common.h). Non-zero: x is the
+  // unpadded activation and every loader reads the mapped source pixel, so dW is the gradient
+  // of the conv of F.pad(x, mode) at padding 0 without the padded copy
+  int pmode = 0;
 };
 
 // one output's share of <G, W> (outputs in the zero-padded channel tail contribute nothing).
@@ -178,12 +182,12 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_mfma(WgradArgs a) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(dyr, (lds_ptr_t)(As + i * 4096 + wid * 1024), 16,
                                                dy_off[i], ks * dy_step, 0, 0);
     if constexpr (ROWS) {
-      const int ih = soh * a.sh - a.ph + ky * a.dh;
+      const int ih = pad_map(soh * a.sh - a.ph + ky * a.dh, a.H, a.pmode);
       const bool rowok = sb < a.Bn && (unsigned)ih < (unsigned)a.H;
       const int soff = rowok ? (sb * a.H + ih) * a.W * a.Cin * 2 : 0;
 #pragma unroll
       for (int i = 0; i < LX; ++i) {
-        const int iw = (sow + xrow0 + i * RSX) * a.sw - a.pw + kx * a.dw;
+        const int iw = pad_map((sow + xrow0 + i * RSX) * a.sw - a.pw + kx * a.dw, a.W, a.pmode);
         const bool ok = rowok && (unsigned)iw < (unsigned)a.W;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(Xs + i * 4096 + wid * 1024), 16,
                                                  ok ? (iw * a.Cin + xc) * 2 : kOobOffset, soff,
@@ -192,8 +196,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_mfma(WgradArgs a) {
     } else {
 #pragma unroll
       for (int i = 0; i < LX; ++i) {
-        const int ih = xoh[i] * a.sh - a.ph + ky * a.dh;
-        const int iw = xow[i] * a.sw - a.pw + kx * a.dw;
+        const int ih = pad_map(xoh[i] * a.sh - a.ph + ky * a.dh, a.H, a.pmode);
+        const int iw = pad_map(xow[i] * a.sw - a.pw + kx * a.dw, a.W, a.pmode);
         const bool ok = xb[i] < a.Bn && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             xrs, (lds_ptr_t)(Xs + i * 4096 + wid * 1024), 16,
@@ -348,10 +352,14 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_mfma(WgradArgs a) {
 // fragments are read from LDS once for all taps. Accumulators: KW x (BNO/2 x BC/2) per wave
 // (tiles: 3 taps 128 x 64, 5 / 7 taps 64 x 64 — the 256-VGPR budget of 2 waves / SIMD, no
 // spills).
-template <int BNO, int BC, int NT, int NST>
+// PM: a.pmode != 0 (reflect / replicate padding mapped by the loader). A template parameter
+// here and in the v2 kernel: as a runtime branch it moved the register allocation of some
+// zero-padding builds.
+template <int BNO, int BC, int NT, int NST, bool PM = false>
 __global__ __launch_bounds__(kThreads, (NT == 5 && BNO == 64) ? 3 : 2) void conv_wgrad_mfma_mt(
     WgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  const int pmode = PM ? a.pmode : 0;
   constexpr int RA = BNO * 2, RX = BC * 2;        // image row bytes
   constexpr int kAbytes = kBP * RA;
   constexpr int kXrows = kBP + 1024 / RX;           // window + one extra wave-DMA of halo rows
@@ -412,20 +420,20 @@ __global__ __launch_bounds__(kThreads, (NT == 5 && BNO == 64) ? 3 : 2) void conv
     for (int i = 0; i < LA; ++i)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(dyr, (lds_ptr_t)(As + i * 4096 + wid * 1024), 16,
                                                dy_off[i], ks * dy_step, 0, 0);
-    const int ih = soh * a.sh - a.ph + ky * a.dh;
+    const int ih = pad_map(soh * a.sh - a.ph + ky * a.dh, a.H, pmode);
     const bool rowok = sb < a.Bn && (unsigned)ih < (unsigned)a.H;
     const int soff = rowok ? (sb * a.H + ih) * a.W * a.Cin * 2 : 0;
     const int iw0 = sow - a.pw;  // input column of window row 0 (stride 1)
 #pragma unroll
     for (int i = 0; i < LX; ++i) {
-      const int iw = iw0 + xrow0 + i * RSX;
+      const int iw = pad_map(iw0 + xrow0 + i * RSX, a.W, pmode);
       const bool ok = rowok && (unsigned)iw < (unsigned)a.W;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(Xs + i * 4096 + wid * 1024), 16,
                                                ok ? (iw * a.Cin + xc) * 2 : kOobOffset, soff, 0,
                                                0);
     }
     if (wid == 0) {
-      const int iw = iw0 + hrow;
+      const int iw = pad_map(iw0 + hrow, a.W, pmode);
       const bool ok = rowok && (unsigned)iw < (unsigned)a.W;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(Xs + kBP * RX), 16,
                                                ok ? (iw * a.Cin + hxc) * 2 : kOobOffset, soff, 0,
@@ -663,9 +671,10 @@ __global__ __launch_bounds__(kThreads, (NT == 5 && BNO == 64) ? 3 : 2) void conv
 // lds (zeros for padding pixels) into an NST-deep ring, drained by a counted vmcnt (never 0
 // in the loop) and a raw s_barrier, so the next k-steps' DMA stays in flight while this one
 // computes; the single wave per SIMD relies on that depth instead of a co-resident block.
-template <int NT, int BC, int WSEG, int NST>
+template <int NT, int BC, int WSEG, int NST, bool PM = false>
 __global__ __launch_bounds__(kThreads, 1) void conv_wgrad_mfma_w4(WgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  const int pmode = PM ? a.pmode : 0;
   constexpr int RB = 256;                                   // dy row bytes (128 channels)
   constexpr int RX = BC * 2;                                // x row bytes
   constexpr int NJ = BC / 32;                               // 16-channel x fragments per wave
@@ -746,8 +755,9 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wgrad_mfma_w4(WgradArgs a) {
     const int imgoff = sb * a.H * rowbytes;
 #pragma unroll
     for (int i = 0; i < LX; ++i) {
-      const int ih = soh + xseg[i] - a.ph + ky * a.dh;        // segment s = output row soh + s
-      const int iw = sow + xcol[i] - a.pw;
+      // segment s = output row soh + s
+      const int ih = pad_map(soh + xseg[i] - a.ph + ky * a.dh, a.H, pmode);
+      const int iw = pad_map(sow + xcol[i] - a.pw, a.W, pmode);
       const bool ok = xseg[i] < R && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
           xrs, (lds_ptr_t)(Xs + i * 4096 + wid * 1024), 16,
@@ -917,11 +927,18 @@ static bool wgrad_v2_shape_ok(int Cout, int Ho, int Wo, int64_t KW, int64_t sh, 
 }
 
 bool conv2d_wgrad_v2_eligible(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
-                              int64_t sh, int64_t sw, int64_t dh, int64_t dw, int64_t nb) {
-  return x.size(1) % 64 == 0 &&
+                              int64_t sh, int64_t sw, int64_t dh, int64_t dw, int64_t nb,
+                              int64_t pad_mode) {
+  // (every k11 loader maps reflect / replicate coordinates itself: pad_mode does not narrow it)
+  return pad_mode >= 0 && pad_mode <= 2 && x.size(1) % 64 == 0 &&
          wgrad_v2_shape_ok((int)dy.size(1), (int)dy.size(2), (int)dy.size(3), KW, sh, sw, dh, dw,
                            nb);
 }
+
+// The k11 kernel of the most recent conv2d_wgrad_mfma launch on this host thread (0 one-tap
+// generic, 1 one-tap ROWS, 2 multi-tap, 3 v2): read by the tests.
+thread_local int g_last_wgrad_kernel = 0;
+int64_t wgrad_last_kernel() { return g_last_wgrad_kernel; }
 
 // variant: 0 = default routing, 1 = never v2, 2 = v2 whenever eligible
 at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
@@ -929,7 +946,7 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
                              int64_t dw, int64_t out_cout, int64_t out_cin, bool out_bf16,
                              int64_t nb, int64_t variant,
                              const c10::optional<std::vector<at::Tensor>>& sn,
-                             const c10::optional<at::Tensor>& dst) {
+                             const c10::optional<at::Tensor>& dst, int64_t pad_mode) {
   IAMD_CHECK(dy.is_cuda() && x.is_cuda(), "conv2d_wgrad_mfma: CUDA tensors expected");
   IAMD_CHECK(dy.scalar_type() == at::kBFloat16 && x.scalar_type() == at::kBFloat16,
              "conv2d_wgrad_mfma: bf16 operands expected");
@@ -949,9 +966,17 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
              "conv2d_wgrad_mfma: dy spatial size does not match the conv geometry");
   IAMD_CHECK(x.numel() * 2 < (1ll << 30) && (dy.numel() + 64ll * Cout) * 2 < (1ll << 30),
              "conv2d_wgrad_mfma: tensors too large for 32-bit buffer offsets");
+  // pad_mode 1 reflect / 2 replicate: x is the unpadded activation (single-weight convs)
+  IAMD_CHECK(pad_mode >= 0 && pad_mode <= 2, "conv2d_wgrad_mfma: pad_mode must be 0 (zeros), 1 "
+             "(reflect) or 2 (replicate), got ", pad_mode);
+  IAMD_CHECK(pad_mode == 0 || nb == 1, "conv2d_wgrad_mfma: pad_mode != 0 needs nb == 1");
+  IAMD_CHECK(pad_mode != 1 || (ph < H && pw < W),
+             "conv2d_wgrad_mfma: reflect padding (", ph, ", ", pw, ") must be smaller than the "
+             "input (", H, ", ", W, ")");
   const int KK = (int)(KH * KW);
   const bool bno128 = Cout % 128 == 0, bc128 = Cin % 128 == 0;
   WgradArgs a;
+  a.pmode = (int)pad_mode;
   a.dy = reinterpret_cast<const __hip_bfloat16*>(dy.data_ptr());
   a.x = reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
   a.dybytes = (int)(dy.numel() / nb * 2);
@@ -1097,6 +1122,7 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
   IAMD_CHECK(gx < (1ll << 31), "conv2d_wgrad_mfma: grid too large");
   const dim3 grid((unsigned)gx, (unsigned)nb);
   const bool rows = Wo % kBP == 0;
+  g_last_wgrad_kernel = v2 ? 3 : mt ? 2 : rows ? 1 : 0;
   // pipeline depth (IMAGINAIRE_AMD_WGRAD_STAGES = 2 | 3). Default 2: the 3-stage ring with
   // counted vmcnt measured 0.98-1.01x the 2-stage loop on every SPADE-step shape
   // (scripts/probe/wgrad_stages_probe.py, profiles/wgrad_stages_probe_mi355x.txt) — two
@@ -1131,7 +1157,10 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
     constexpr int BNO = decltype(bv)::value;
     constexpr int BC = decltype(cv)::value;
     constexpr int NT = decltype(tv)::value;
-    if (nst == 3)
+    if (a.pmode != 0)  // (two stages only)
+      hipLaunchKernelGGL((conv_wgrad_mfma_mt<BNO, BC, NT, 2, true>), grid, dim3(kThreads), 0,
+                         stream(), a);
+    else if (nst == 3)
       hipLaunchKernelGGL((conv_wgrad_mfma_mt<BNO, BC, NT, 3>), grid, dim3(kThreads), 0,
                          stream(), a);
     else
@@ -1144,13 +1173,21 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
       constexpr int WS = decltype(sv)::value;
       if constexpr (NT == 3) {
         if (v2_bc == 128) {
-          hipLaunchKernelGGL((conv_wgrad_mfma_w4<NT, 128, WS, 3>), grid, dim3(kThreads), 0,
-                             stream(), a);
+          if (a.pmode != 0)
+            hipLaunchKernelGGL((conv_wgrad_mfma_w4<NT, 128, WS, 3, true>), grid, dim3(kThreads),
+                               0, stream(), a);
+          else
+            hipLaunchKernelGGL((conv_wgrad_mfma_w4<NT, 128, WS, 3>), grid, dim3(kThreads), 0,
+                               stream(), a);
           return;
         }
       }
-      hipLaunchKernelGGL((conv_wgrad_mfma_w4<NT, 64, WS, 3>), grid, dim3(kThreads), 0,
-                         stream(), a);
+      if (a.pmode != 0)
+        hipLaunchKernelGGL((conv_wgrad_mfma_w4<NT, 64, WS, 3, true>), grid, dim3(kThreads), 0,
+                           stream(), a);
+      else
+        hipLaunchKernelGGL((conv_wgrad_mfma_w4<NT, 64, WS, 3>), grid, dim3(kThreads), 0,
+                           stream(), a);
     };
     using S64 = std::integral_constant<int, 64>;
     using S32 = std::integral_constant<int, 32>;

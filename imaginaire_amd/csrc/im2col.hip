@@ -18,6 +18,7 @@ namespace {
 
 struct PackGeom {
   int B, Cin, H, W, Ho, Wo, KH, KW, sh, sw, ph, pw, dh, dw, K, Kp;
+  int pmode = 0;  // 0 zeros, 1 reflect, 2 replicate (pad_map): padding pixels gathered from x
   int64_t sb, sc, sy, sx;  // element strides of x / dx (any layout)
 };
 
@@ -44,7 +45,8 @@ __global__ void __launch_bounds__(256) im2col_pack_kernel(const T* __restrict__ 
       if (k < g.K) {
         const int tap = k / g.Cin, ci = k - tap * g.Cin;
         const int ky = tap / g.KW, kx = tap - ky * g.KW;
-        const int ih = oh * g.sh - g.ph + ky * g.dh, iw = ow * g.sw - g.pw + kx * g.dw;
+        const int ih = pad_map(oh * g.sh - g.ph + ky * g.dh, g.H, g.pmode);
+        const int iw = pad_map(ow * g.sw - g.pw + kx * g.dw, g.W, g.pmode);
         if ((unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W)
           v[e] = to_f<T>(x[b * g.sb + ci * g.sc + ih * g.sy + iw * g.sx]);
       }
@@ -74,8 +76,10 @@ int grid_for(int64_t total) {
 
 // x [B, Cin, H, W] (fp32 / bf16, any layout), Cin <= 16 -> col [B, Kp, Ho, Wo] channels-last
 // bf16 with col[m][(ky * KW + kx) * Cin + ci] = x[b, ci, oh*sh - ph + ky*dh, ow*sw - pw + kx*dw]
+// (pad_mode 0: zeros outside the image; 1 reflect / 2 replicate: the mapped pixel of x)
 at::Tensor im2col_pack(const at::Tensor& x, int64_t KH, int64_t KW, int64_t sh, int64_t sw,
-                       int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t Kp) {
+                       int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t Kp,
+                       int64_t pad_mode) {
   IAMD_CHECK(x.is_cuda() && x.dim() == 4, "im2col_pack: 4-D CUDA tensor expected");
   IAMD_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16,
              "im2col_pack: fp32 / bf16 input");
@@ -83,7 +87,10 @@ at::Tensor im2col_pack(const at::Tensor& x, int64_t KH, int64_t KW, int64_t sh, 
   IAMD_CHECK(Cin >= 1 && Cin <= 16, "im2col_pack: Cin must be 1..16");
   IAMD_CHECK(Kp % 64 == 0 && Kp >= KH * KW * Cin && sh >= 1 && sw >= 1 && dh >= 1 && dw >= 1,
              "im2col_pack: bad geometry");
+  IAMD_CHECK(pad_mode >= 0 && pad_mode <= 2 && (pad_mode != 1 || (ph < H && pw < W)),
+             "im2col_pack: pad_mode must be 0 / 1 (reflect, padding smaller than the input) / 2");
   PackGeom g = make_geom(B, Cin, H, W, KH, KW, sh, sw, ph, pw, dh, dw, Kp);
+  g.pmode = (int)pad_mode;
   IAMD_CHECK(g.Ho > 0 && g.Wo > 0, "im2col_pack: empty output");
   g.sb = x.stride(0); g.sc = x.stride(1); g.sy = x.stride(2); g.sx = x.stride(3);
   auto col = at::empty({B, Kp, g.Ho, g.Wo},

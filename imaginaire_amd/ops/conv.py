@@ -10,6 +10,10 @@ Every 2-D convolution issued by the framework's layers goes through here.
   weight gradient runs the k11 kernel (``csrc/conv_wgrad_mfma.hip``: transposing LDS reads,
   split-K over pixels) or MIOpen's wrw, whichever was measured faster for the shape (first
   call). The activation backward + bias gradient is the k2 epilogue kernel.
+  ``padding_mode='reflect'`` / ``'replicate'``: the k10 / k11 / im2col_pack loaders read the
+  padding pixels of the unpadded activation themselves (``_fused_pad_mode``, ``_FUSED_PAD``);
+  only the data gradient is still computed over the padded extent and folded by
+  ``pad_nhwc_bwd``. Anything those loaders do not take pads first (``pad``), then convolves.
 * **MIOpen path.** Everything else. MIOpen's fast NHWC solvers require *packed* NHWC
   activations AND weights, otherwise they fall back to naive direct kernels (measured
   at >95% of a SPADE step on MI355X, profiles/spade_step_naive_conv_mi355x.txt), so both
@@ -469,8 +473,11 @@ class _MfmaConv2d(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, w, bias, stride, padding, dilation, slope, res=None, sw=None):
+    def forward(ctx, x, w, bias, stride, padding, dilation, slope, res=None, sw=None, pmode=0):
+        # pmode 1 reflect / 2 replicate: k10 / k11 read the padding pixels of the unpadded x
+        # themselves (the conv of F.pad(x, mode) at padding 0, no padded copy made or saved)
         cout, cin = w.shape[0], w.shape[1]
+        assert not pmode or cout > 16, 'thin-output convs keep the explicit pad'
         cp, op = _round_up(cin, 64), _out_pad(cout)
         xb = _pad_channels(x, cp, torch.bfloat16)
         sig = None if sw is None else sw.sigma.reshape(1)
@@ -483,13 +490,15 @@ class _MfmaConv2d(torch.autograd.Function):
         # Cout % 8 == 0: k10 stores only the real output channels (no crop copy after it)
         ncv = cout if (op != cout and cout % 8 == 0) else op
         ctx.res_dtype = None if res is None else res.dtype
+        ctx.pmode = pmode
         with _Logged('fwd', 'k10', 2.0 * x.shape[0] * ho * wo * op * cp * w.shape[2] * w.shape[3],
-                     _gemm_desc(xb, wb, stride, padding) + ('' if sw is None else ' sn')):
+                     _gemm_desc(xb, wb, stride, padding) + ('' if sw is None else ' sn') +
+                     ('', ' reflect', ' replicate')[pmode]):
             bp = None if bias is None else _frozen_prep(bias, ('b', op),
                                                         lambda: _pad_rows(bias, op).float())
             y = _ext.ext().conv2d_mfma(xb, wb, bp, stride[0], stride[1],
                                        padding[0], padding[1], dilation[0], dilation[1],
-                                       float(slope), 1, ncv, res, sig)
+                                       float(slope), 1, ncv, res, sig, pmode)
         ctx.conf = (stride, padding, dilation, float(slope), cin, cout, x.dtype, w.dtype,
                     None if bias is None else bias.dtype, x.shape[1])
         ctx.sn = None if sw is None else (sw.shadow, sw.u, sw.v, sig)
@@ -516,6 +525,15 @@ class _MfmaConv2d(torch.autograd.Function):
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         sn = ctx.sn
         sig = None if sn is None else sn[3]
+        pmode = ctx.pmode
+        # fused reflect / replicate padding: the data gradient is computed over the padded
+        # extent (gh, gw) at padding 0, exactly as for the conv of a padded copy, and folded
+        # onto the input by pad_nhwc_bwd; the weight gradient is k11 on the unpadded xb
+        wpad = padding
+        gh, gw = xb.shape[2], xb.shape[3]
+        if pmode:
+            gh, gw = gh + 2 * padding[0], gw + 2 * padding[1]
+            padding = (0, 0)
         # the activation backward runs at the saved output's channel count (the real Cout when
         # k10 stored only those, else the padded one), then dy is padded for the GEMMs; without
         # an activation / bias gradient that is ONE pad-cast pass from any dy layout
@@ -559,11 +577,12 @@ class _MfmaConv2d(torch.autograd.Function):
                 if side_bias:  # bias gradient only: the k2 kernel reads dy, writes no dx
                     db = _ext.ext().bias_act_bwd(dy, dy, 1.0)[1]
                 if need_w_left and _OVERLAP_BWD in ('1', 'small'):
-                    dw = _wgrad(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn)
+                    dw = _wgrad(dy, xb, wb, stride, wpad, dilation, cout, cin, wdt, sn,
+                                pmode=pmode)
         if need_x_left:
             pt = (dilation[0] * (kh - 1) - padding[0], dilation[1] * (kw - 1) - padding[1])
             cp = wb.shape[1]
-            dblocks = -(-dy.shape[0] * xb.shape[2] * xb.shape[3] // 128) * \
+            dblocks = -(-dy.shape[0] * gh * gw // 128) * \
                 (cp // (128 if cp % 128 == 0 else 64))
             # the dgrad GEMM has N = Cin (few tiles, K = taps x Cout for the SPADE γ/β convs):
             # k10 splits K over the grid's y dimension for those
@@ -591,19 +610,33 @@ class _MfmaConv2d(torch.autograd.Function):
             elif _STRIDED_DGRAD and stride[0] == stride[1] and 2 <= stride[0] <= 4 and \
                     dilation == (1, 1) and (cap or (
                         dblocks >= _MFMA_MIN_DGRAD_BLOCKS * stride[0] ** 2 and
-                        xb.shape[0] * xb.shape[2] * xb.shape[3] >= _STRIDED_DGRAD_MIN_PIX)):
+                        xb.shape[0] * gh * gw >= _STRIDED_DGRAD_MIN_PIX)):
                 # large maps only: 1.3-1.6x MIOpen on the full-resolution PatchGAN layers, on par
                 # or slower below ~128K dx pixels (profiles/strided_dgrad_probe_mi355x.txt)
                 with _Logged('dgrad', 'k10s', fl, _gemm_desc(dy, wb, stride, padding)):
-                    dx = _strided_dgrad(dy, wb, xb.shape[2], xb.shape[3], stride[0], padding,
-                                        ncv=ncv, ascale=sig)
+                    dx = _strided_dgrad(dy, wb, gh, gw, stride[0], padding, ncv=ncv, ascale=sig)
             else:
                 with _Logged('dgrad', 'miopen', fl, _gemm_desc(dy, wb, stride, padding)):
+                    # (with fused padding only the padded extent's shape is needed)
+                    xg = xb if not pmode else torch.empty(
+                        (xb.shape[0], xb.shape[1], gh, gw), dtype=xb.dtype, device=xb.device,
+                        memory_format=_CL)
                     dx = torch.ops.aten.convolution_backward(
-                        dy, xb, wb, None, stride, padding, dilation, False, [0, 0], 1,
+                        dy, xg, wb, None, stride, padding, dilation, False, [0, 0], 1,
                         [True, False, False])[0]
                     if sig is not None:
                         dx = dx.div_(sig)  # one pass (fp32 divisor, no reciprocal / cast kernels)
+            if pmode:
+                # fold the padded-extent gradient onto the input (the adjoint of the padding),
+                # in the order and dtype the pad-then-conv path folds it
+                if dx.shape[1] != xc:
+                    dx = dx[:, :xc]
+                dx = _ext.ext().pad_nhwc_bwd(
+                    dx.to(xdt).contiguous(memory_format=_CL), xb.shape[2], xb.shape[3], wpad[1],
+                    wpad[1], wpad[0], wpad[0], pmode - 1)
+            # (fused padding: folding is the adjoint of padding, so <folded dx, x> = <dx, pad(x)>.
+            # The fold runs in the input's dtype, as pad-then-conv's does, so for an fp32 input
+            # the folded dx is fp32 and <G, W> comes from the k11 epilogue instead)
             if sn is not None and need_w and dw is None and _SN_DOT_RATIO > 0 and \
                     xb.numel() <= _SN_DOT_RATIO * wb.numel() and dx.dtype == torch.bfloat16 and \
                     dx.shape[1] % 8 == 0 and dx.is_contiguous(memory_format=_CL):
@@ -625,7 +658,8 @@ class _MfmaConv2d(torch.autograd.Function):
         if need_w:
             if dw is None:
                 dest = _take_grad_dest(ctx.wparam, (cout, cin, wb.shape[2], wb.shape[3]))
-                dw = _wgrad(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn, dest)
+                dw = _wgrad(dy, xb, wb, stride, wpad, dilation, cout, cin, wdt, sn, dest,
+                            pmode=pmode)
             elif not need_w_left:  # (thin-output path: already cropped, in fp32)
                 pass
             if dw.shape[0] != cout or dw.shape[1] != cin:
@@ -646,7 +680,7 @@ class _MfmaConv2d(torch.autograd.Function):
         dres = None
         if ctx.res_dtype is not None and ctx.needs_input_grad[7]:
             dres = dy_in if dy_in.dtype == ctx.res_dtype else dy_in.to(ctx.res_dtype)
-        return dx, dw, db, None, None, None, None, dres, None
+        return dx, dw, db, None, None, None, None, dres, None, None
 
 
 # Negative control of the model-parity gate (tests/test_model_parity_gpu.py): with
@@ -947,12 +981,14 @@ class _TapPackConv2d(torch.autograd.Function):
     data gradient (a thin-output conv of dy) runs on the k10 dgrad."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, stride, padding, dilation, slope):
+    def forward(ctx, x, w, bias, stride, padding, dilation, slope, pmode=0):
+        # pmode 1 reflect / 2 replicate: im2col_pack gathers the padding pixels from x itself
         cout, cin, kh, kw = w.shape
         kp, op = _round_up(kh * kw * cin, 64), _out_pad(cout)
         X = _ext.ext()
         col = X.im2col_pack(x.detach(), kh, kw, stride[0], stride[1], padding[0], padding[1],
-                            dilation[0], dilation[1], kp)
+                            dilation[0], dilation[1], kp, pmode)
+        ctx.pmode = pmode
         wp = _frozen_prep(w, ('tp', kp, op), lambda: _pack_taps(w, kp, op))
         ncv = cout if (op != cout and cout % 8 == 0) else op
         with _Logged('fwd', 'k10p', 2.0 * col.shape[0] * col.shape[2] * col.shape[3] * op * kp,
@@ -983,6 +1019,10 @@ class _TapPackConv2d(torch.autograd.Function):
             db = X.bias_act_bwd(dy, dy, 1.0)[1]
         dy = _pad_channels(dy, op, torch.bfloat16)
         dx = dw = None
+        pmode, fold = ctx.pmode, None
+        if pmode:  # data gradient over the padded extent at padding 0, folded below
+            fold = (H, W, padding[1], padding[1], padding[0], padding[0], pmode - 1)
+            H, W, padding = H + 2 * padding[0], W + 2 * padding[1], (0, 0)
         if need_x:
             # the data gradient of a thin INPUT is a thin-output conv of dy: on the usual k10
             # dgrad (flipped weight, output channels padded to 64). (The adjoint of the packing —
@@ -1011,6 +1051,8 @@ class _TapPackConv2d(torch.autograd.Function):
                     wb, None, stride, padding, dilation, False, [0, 0], 1,
                     [True, False, False])[0]
             dx = dx[:, :cin].to(xdt)
+            if fold is not None:
+                dx = X.pad_nhwc_bwd(dx.contiguous(memory_format=_CL), *fold)
         if need_w:
             with _Logged('wgrad', 'k11', 2.0 * col.shape[0] * col.shape[2] * col.shape[3] * op *
                          kp, '%s tappack' % list(col.shape)):
@@ -1021,7 +1063,7 @@ class _TapPackConv2d(torch.autograd.Function):
                 dw = _test_flip_wgrad(dw)
         if db is not None:
             db = db[:cout].to(bdt) if need_b else None
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
 _TAPPACK = os.environ.get('IMAGINAIRE_AMD_TAPPACK', '1') == '1'
@@ -1159,27 +1201,31 @@ def _agree(times):
 
 
 def _wgrad_fns(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, variant=0, sn=None,
-               dest=None):
+               dest=None, pmode=0):
     def k11(v=variant):
         return _ext.ext().conv2d_wgrad_mfma(dy, xb, wb.shape[2], wb.shape[3], stride[0],
                                             stride[1], padding[0], padding[1], dilation[0],
                                             dilation[1], cout, cin, wdt == torch.bfloat16, 1, v,
-                                            None if sn is None else list(sn), dest)
+                                            None if sn is None else list(sn), dest, pmode)
 
     def miopen():
+        xg, pd = xb, padding
+        if pmode:  # (MIOpen knows zero padding only: the padded copy, then padding 0)
+            xg, pd = _ext.ext().pad_nhwc_fwd(xb, padding[1], padding[1], padding[0], padding[0],
+                                             pmode - 1), (0, 0)
         return torch.ops.aten.convolution_backward(
-            dy, xb, wb, None, stride, padding, dilation, False, [0, 0], 1,
+            dy, xg, wb, None, stride, pd, dilation, False, [0, 0], 1,
             [False, True, False])[1]
     return k11, miopen
 
 
-def _k11_variants(dy, xb, wb, stride, dilation):
+def _k11_variants(dy, xb, wb, stride, dilation, pmode=0):
     """k11 kernel variants that can run this weight gradient: 'k11' (multi-tap / one-tap, two
     or three blocks per CU) and, where eligible, 'k11v2' (one block per CU, 64 x 64 x KW-tap
     accumulators per wave). Neither wins everywhere (profiles/wgrad_readahead_probe_mi355x.txt),
     so the autotuner times both per shape."""
     if _ext.ext().conv2d_wgrad_v2_eligible(dy, xb, wb.shape[2], wb.shape[3], stride[0],
-                                           stride[1], dilation[0], dilation[1]):
+                                           stride[1], dilation[0], dilation[1], 1, pmode):
         return ('k11', 'k11v2')
     return ('k11',)
 
@@ -1204,29 +1250,31 @@ def _take_grad_dest(p, shape):
 
 
 def _wgrad(dy, xb, wb, stride, padding, dilation, cout=-1, cin=-1, wdt=torch.float32, sn=None,
-           dest=None):
+           dest=None, pmode=0):
     """Weight gradient: k11 or MIOpen wrw (``IMAGINAIRE_AMD_MFMA_WGRAD`` = 1 | 0 | auto; auto =
     the faster of the two per shape, timed by :func:`tune_pending` outside the backward and
     agreed across ranks). k11 returns the gradient already cropped to (cout, cin) and in the
     weight's dtype (bf16 for the bf16 spectral-norm / autocast weights): the crop and cast ride
     in its split-K sum. ``sn`` = (bf16 shadow, u, v, sigma) of a spectrally normalised weight
-    (:class:`_MfmaConv2d`): k11 only, returning the fp32 gradient w.r.t. W."""
+    (:class:`_MfmaConv2d`): k11 only, returning the fp32 gradient w.r.t. W. ``pmode`` 1 / 2:
+    ``xb`` is the unpadded input of a reflect / replicate padded conv (k11 maps the padding)."""
     k11, miopen = _wgrad_fns(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn=sn,
-                             dest=dest)
+                             dest=dest, pmode=pmode)
     mode = _MFMA_WGRAD if sn is None else '1'  # (the SN backward rides in k11's split-K sum)
     fl = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * wb.numel()
     desc = _gemm_desc(xb, wb, stride, padding)
     if mode == '0' and not _capturing():
         with _Logged('wgrad', 'miopen', fl, desc):
             return miopen()
-    variants = _k11_variants(dy, xb, wb, stride, dilation)
+    variants = _k11_variants(dy, xb, wb, stride, dilation, pmode)
     if mode == '1' and len(variants) == 1:
         with _Logged('wgrad', 'k11', fl, desc):
             return k11()
     # per-shape choice among the candidates (mode 1: the k11 variants; auto: those and MIOpen),
     # timed by tune_pending() between iterations; the default routing runs until then
     key = (tuple(dy.shape), tuple(xb.shape), tuple(wb.shape), stride, padding, dilation,
-           cout, cin, wdt) + (() if sn is None else ('sn',) if len(sn) == 4 else ('sndx',))
+           cout, cin, wdt) + (() if sn is None else ('sn',) if len(sn) == 4 else ('sndx',)) + \
+        (('pm%d' % pmode,) if pmode else ())
     # ('sn': tuned with the k11 <G, W> epilogue; 'sndx': <G, W> came from the data gradient)
     choice = _WGRAD_CHOICE.get(key)
     if choice is None:
@@ -1321,12 +1369,13 @@ def tune_pending():
                     torch.bfloat16).contiguous(memory_format=cl),
                     torch.randn(cout, device=dev), torch.randn(cin * kk, device=dev),
                     torch.ones(1, device=dev))
+            pm = 1 if 'pm1' in key[9:] else 2 if 'pm2' in key[9:] else 0  # fused padding mode
             k11, miopen = _wgrad_fns(dy, xb, wb, stride, padding, dilation, cout, cin, wdt,
-                                     sn=sn)
+                                     sn=sn, pmode=pm)
             fns = {}
             if _MFMA_WGRAD != '1' and sn is None:
                 fns['miopen'] = miopen
-            if len(_k11_variants(dy, xb, wb, stride, dilation)) > 1:
+            if len(_k11_variants(dy, xb, wb, stride, dilation, pm)) > 1:
                 fns['k11'] = lambda: k11(1)
                 fns['k11v2'] = lambda: k11(2)
             else:
@@ -1413,6 +1462,43 @@ def pad(x, pad_lrtb, mode):
 
 
 _RESIDUAL_EPILOGUE = os.environ.get('IMAGINAIRE_AMD_CONV_RESIDUAL', '1') == '1'
+# reflect / replicate padding read in place by the k10 / k11 / im2col_pack loaders (no padded
+# copy of the activation); 0: pad-then-conv everywhere
+_FUSED_PAD = os.environ.get('IMAGINAIRE_AMD_CONV_FUSED_PAD', '1') != '0'
+_FUSED_PAD_MODES = {'reflect': 1, 'replicate': 2}
+
+
+def _fused_pad_mode(x, weight, stride, padding, dilation, groups, padding_mode):
+    """The kernels' padding mode (1 reflect / 2 replicate) when this padded conv can read its
+    padding in place, else 0 (pad-then-conv): symmetric padding within the single-reflection
+    bound, native bf16 compute, Cout > 16 (thin-output heads and tap-split keep the explicit
+    pad), and a conv that reaches :class:`_TapPackConv2d` or :class:`_MfmaConv2d` (k10 then
+    runs the tile the pad-then-conv route would, except that v3 falls to v1). ``weight``
+    is the conv's weight or an :class:`SNWeight` (judged by its bf16 shadow)."""
+    pm = _FUSED_PAD_MODES.get(padding_mode, 0)
+    if isinstance(weight, SNWeight):
+        weight = weight.shadow
+    if not (pm and _FUSED_PAD and groups == 1 and torch.is_tensor(x) and x.is_cuda and
+            x.dim() == 4 and weight.dim() == 4 and _ext.use_native(x) and
+            x.dtype in (torch.bfloat16, torch.float32)):  # (the dtypes pad_nhwc_bwd folds)
+        return 0
+    ph, pw = padding
+    cout, cin, kh, kw = weight.shape
+    if ph < 0 or pw < 0 or (ph == 0 and pw == 0) or cout <= 16 or \
+            ph >= x.shape[2] or pw >= x.shape[3] or (pm == 2 and max(ph, pw) >= 15) or \
+            _compute_dtype(x, weight) != torch.bfloat16:
+        return 0
+    if tappack_eligible(_thin_view(x, cin), weight, stride, padding, dilation, 1):
+        return pm
+    cx = x.shape[1]
+    if cx != cin and not (cx == _round_up(cin, 64) and
+                          getattr(x, '_iamd_valid_channels', None) == cin):
+        return 0
+    wm = torch.empty((cout, cx, kh, kw), dtype=torch.bfloat16, device='meta')
+    if tapsplit_eligible(x, wm, stride, padding, dilation, 1) or \
+            not mfma_eligible(x, wm, stride, padding, dilation, 1):
+        return 0
+    return pm
 
 
 def _residual_fusible(res, x, weight, stride, padding, dilation):
@@ -1436,7 +1522,18 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1,
     if isinstance(weight, SNWeight):
         st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
         if groups == 1 and x.is_cuda and x.dim() == 4:
-            if padding_mode not in ('zeros', None):  # reflect / replicate: pad, then the conv
+            pm = 0 if padding_mode in ('zeros', None) else _fused_pad_mode(
+                x, weight, st, pd, dl, groups, padding_mode)
+            if pm and _sn_fused_ok(x, weight, st, pd, dl, residual):
+                # reflect / replicate padding read by the k10 / k11 loaders themselves
+                return _MfmaConv2d.apply(nhwc(x), weight.W, bias, st, pd, dl, 1.0, residual, weight,
+                                         pm)
+            # a thin-input conv takes the materialised weight to the tap-packed path below, which
+            # gathers the padding itself: no explicit pad here
+            thin = pm and tappack_eligible(_thin_view(x, weight.shape[1]), weight.shadow, st, pd,
+                                           dl, 1)
+            if padding_mode not in ('zeros', None) and not thin:
+                # reflect / replicate: pad, then the conv
                 vc = getattr(x, '_iamd_valid_channels', None)
                 x = pad(nhwc(x), _pad_arg(padding), padding_mode)
                 if vc is not None:
@@ -1453,8 +1550,24 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1,
                     mfma_eligible(x, w, st, pd, dl, groups) and \
                     _residual_fusible(residual, x, w, st, pd, dl):
                 return _MfmaConv2d.apply(x, w, bias, st, pd, dl, 1.0, residual)
+        elif groups == 1 and x.is_cuda and x.dim() == 4 and weight.dim() == 4:
+            # reflect / replicate padding read by the k10 loader: the residual epilogue as well
+            pm = _fused_pad_mode(x, weight, st, pd, dl, groups, padding_mode)
+            if pm and not tappack_eligible(_thin_view(x, weight.shape[1]), weight, st, pd, dl, 1):
+                w = _match_channels(x, weight)
+                if _residual_fusible(residual, x, w, st, pd, dl):
+                    return _MfmaConv2d.apply(nhwc(x), w, bias, st, pd, dl, 1.0, residual, None, pm)
         return conv2d(x, weight, bias, stride, padding, dilation, groups, padding_mode) + residual
     if padding_mode != 'zeros' and padding_mode is not None:
+        st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
+        pm = 0 if not (x.is_cuda and x.dim() == 4 and weight.dim() == 4) else _fused_pad_mode(
+            x, weight, st, pd, dl, groups, padding_mode)
+        if pm:  # reflect / replicate padding read by the loaders themselves: no padded copy
+            xt = _thin_view(x, weight.shape[1])
+            if tappack_eligible(xt, weight, st, pd, dl, 1):
+                return _TapPackConv2d.apply(xt, weight, bias, st, pd, dl, 1.0, pm)
+            return _MfmaConv2d.apply(nhwc(x), _match_channels(x, weight), bias, st, pd, dl, 1.0,
+                                     None, None, pm)
         vc = getattr(x, '_iamd_valid_channels', None)
         x = pad(nhwc(x), _pad_arg(padding), padding_mode)
         if vc is not None:
