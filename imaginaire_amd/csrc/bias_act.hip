@@ -162,7 +162,67 @@ bool is_cl(const at::Tensor& x) {
   return x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast) && !x.is_contiguous();
 }
 
+// Host-side plan of bias_act_bwd for an output tensor and a slope. chan_fast (channels-last or
+// [N, C] linear): bias_act_bwd_cl on a (P, nzc) grid, tpr threads per row, rows_per_block rows
+// per block, variant (act, unroll); else bias_act_bwd_nchw on an (N, C) grid (P = N partial rows,
+// always with the activation gradient).
+struct BwdPlan {
+  bool chan_fast;
+  int vec, tpr, nzc, P;
+  int64_t rows, rows_per_block;
+  bool act, unroll;
+};
+
+BwdPlan bwd_plan(const at::Tensor& out, double slope) {
+  BwdPlan p;
+  p.chan_fast = is_cl(out) || out.dim() == 2;
+  const int N = (int)out.size(0), C = (int)out.size(1);
+  const int64_t HW = out.numel() / std::max<int64_t>(1, (int64_t)N * C);
+  p.vec = 16 / (int)out.element_size();
+  if (p.chan_fast) {
+    while (p.vec > 1 && (C % p.vec)) p.vec >>= 1;
+    p.tpr = std::max(1, std::min(C / p.vec, kThreads));
+    p.nzc = ceil_div(C, (int64_t)p.tpr * p.vec);
+    p.rows = (int64_t)N * HW;
+    const int rpb = kThreads / p.tpr;
+    p.rows_per_block = std::max<int64_t>(rpb * 4, (p.rows + 511) / 512);
+    p.P = (int)((p.rows + p.rows_per_block - 1) / p.rows_per_block);
+    p.act = slope != 1.0;
+    // IMAGINAIRE_AMD_BIASACT_UNROLL (read per call, A/B): rows per trip, 4 or 1. Default: 4 for
+    // the bias-only pass (1.00-1.17x), 1 with an activation (already 4.7-5.7 TB/s; 0.97-1.00x
+    // unrolled): profiles/bias_act_bwd_unroll_ab_r6_mi355x.txt
+    const char* ue = std::getenv("IMAGINAIRE_AMD_BIASACT_UNROLL");
+    p.unroll = ue == nullptr ? !p.act : std::atoi(ue) != 1;
+  } else {
+    while (p.vec > 1 && (HW % p.vec)) p.vec >>= 1;
+    p.tpr = 0;
+    p.nzc = C;
+    p.rows = 0;
+    p.rows_per_block = 0;
+    p.P = N;
+    p.act = true;
+    p.unroll = false;
+  }
+  return p;
+}
+
 }  // namespace
+
+// bwd_plan as name -> value for the tests (they assert the path a shape is named for);
+// launches nothing.
+py::dict bias_act_plan(const at::Tensor& x, double slope) {
+  IAMD_CHECK(is_cl(x) || x.is_contiguous(), "bias_act: x must be contiguous or channels_last");
+  const BwdPlan p = bwd_plan(x, slope);
+  py::dict d;
+  d["vec"] = p.vec;
+  d["tpr"] = p.tpr;
+  d["nzc"] = p.nzc;
+  d["rows_per_block"] = p.rows_per_block;
+  d["P"] = p.P;
+  d["act"] = p.act;
+  d["unroll"] = p.unroll;
+  return d;
+}
 
 // x: [N, C, ...] (NCHW / channels_last / [N, C] for linear). Returns out (may alias x).
 at::Tensor bias_act_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& bias, double slope,
@@ -224,28 +284,18 @@ std::vector<at::Tensor> bias_act_bwd(const at::Tensor& out, const at::Tensor& dy
   // so no later allocation of the (graph) pool can reuse their block while the column sum
   // might still read them
   at::Tensor buf, partial;
-  int P;
+  const BwdPlan plan = bwd_plan(out, slope);
+  const int P = plan.P, vec = plan.vec;
   IAMD_DISPATCH_FLOAT_TYPES(out.scalar_type(), "bias_act_bwd", [&] {
     auto op = reinterpret_cast<const scalar_t*>(out.data_ptr());
     auto gp = reinterpret_cast<const scalar_t*>(dy.data_ptr());
     auto dp = reinterpret_cast<scalar_t*>(dx.data_ptr());
     if (cl || lin) {
-      int vec = 16 / (int)out.element_size();
-      while (vec > 1 && (C % vec)) vec >>= 1;
-      const int tpr = std::max(1, std::min(C / vec, kThreads));
-      const int nzc = ceil_div(C, (int64_t)tpr * vec);
-      const int64_t rows = (int64_t)N * HW;
-      const int rpb = kThreads / tpr;
-      int64_t rows_per_block = std::max<int64_t>(rpb * 4, (rows + 511) / 512);
-      P = (int)((rows + rows_per_block - 1) / rows_per_block);
+      const int tpr = plan.tpr, nzc = plan.nzc;
+      const int64_t rows = plan.rows, rows_per_block = plan.rows_per_block;
       buf = at::empty({(int64_t)P * C + C}, fopt);
       partial = buf.narrow(0, 0, (int64_t)P * C);
-      const bool act = slope != 1.0;
-      // IMAGINAIRE_AMD_BIASACT_UNROLL (read per call, A/B): rows per trip, 4 or 1. Default: 4 for
-      // the bias-only pass (1.00-1.17x), 1 with an activation (already 4.7-5.7 TB/s; 0.97-1.00x
-      // unrolled): profiles/bias_act_bwd_unroll_ab_r6_mi355x.txt
-      const char* ue = std::getenv("IMAGINAIRE_AMD_BIASACT_UNROLL");
-      const bool unroll = ue == nullptr ? !act : std::atoi(ue) != 1;
+      const bool act = plan.act, unroll = plan.unroll;
       auto launch = [&](auto vt) {
         constexpr int V = decltype(vt)::value;
         auto go = [&](auto kern) {
@@ -264,9 +314,6 @@ std::vector<at::Tensor> bias_act_bwd(const at::Tensor& out, const at::Tensor& dy
         default: launch(std::integral_constant<int, 1>()); break;
       }
     } else {
-      int vec = 16 / (int)out.element_size();
-      while (vec > 1 && (HW % vec)) vec >>= 1;
-      P = N;
       buf = at::empty({(int64_t)N * C + C}, fopt);
       partial = buf.narrow(0, 0, (int64_t)N * C);
       auto launch = [&](auto vt) {

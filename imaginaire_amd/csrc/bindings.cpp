@@ -12,6 +12,7 @@ std::vector<at::Tensor> norm_stats(const at::Tensor& x, bool per_instance, doubl
                                    const c10::optional<at::Tensor>& running_var,
                                    const c10::optional<at::Tensor>& num_batches,
                                    double momentum);
+py::dict norm_plan(const at::Tensor& x, bool per_instance);
 std::vector<at::Tensor> sync_stats_merge(const at::Tensor& allst, double eps,
                                          const c10::optional<at::Tensor>& weight,
                                          const c10::optional<at::Tensor>& bias,
@@ -43,6 +44,7 @@ at::Tensor norm_bwd_apply(const at::Tensor& x, const at::Tensor& dout, const at:
 at::Tensor bias_act_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& bias, double slope,
                         bool inplace);
 std::vector<at::Tensor> bias_act_bwd(const at::Tensor& out, const at::Tensor& dy, double slope);
+py::dict bias_act_plan(const at::Tensor& x, double slope);
 // partial_conv.hip (k3)
 std::vector<at::Tensor> partial_conv_renorm(const at::Tensor& raw, const at::Tensor& mask,
                                             const c10::optional<at::Tensor>& bias, int64_t kh,
@@ -288,12 +290,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias"), py::arg("partial_only"), py::arg("running_mean") = py::none(),
         py::arg("running_var") = py::none(), py::arg("num_batches") = py::none(),
         py::arg("momentum") = 0.0);
+  m.def("norm_plan", &iamd::norm_plan,
+        "host-side plan of norm_stats / norm_bwd_reduce for x (launches nothing): cl, vec, tpr, "
+        "rpb, nzc, chunk, P, rs_stats, rs_bwd",
+        py::arg("x"), py::arg("per_instance"));
   m.def("norm_bwd_coeffs", &iamd::norm_bwd_coeffs, "k1 backward coefficients from the sums");
   m.def("norm_apply", &iamd::norm_apply, "norm + SPADE modulation + activation (k1 fwd)");
   m.def("norm_bwd_reduce", &iamd::norm_bwd_reduce, "k1 backward reduction");
   m.def("norm_bwd_apply", &iamd::norm_bwd_apply, "k1 backward dx");
   m.def("bias_act_fwd", &iamd::bias_act_fwd, "bias + activation epilogue (k2)");
   m.def("bias_act_bwd", &iamd::bias_act_bwd, "k2 backward: dx and dbias");
+  m.def("bias_act_plan", &iamd::bias_act_plan,
+        "host-side plan of bias_act_bwd for an output x (launches nothing): vec, tpr, nzc, "
+        "rows_per_block, P, act, unroll",
+        py::arg("x"), py::arg("slope"));
   m.def("partial_conv_renorm", &iamd::partial_conv_renorm, "partial conv mask/renorm (k3)");
   m.def("mt_adam", &iamd::mt_adam, "multi-tensor Adam/AdamW (k4)", py::arg("params"),
         py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("shadows"),

@@ -700,6 +700,19 @@ int apply_grid(int64_t total_vec) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(blocks, 256 * 16));
 }
 
+// two-stage statistics merge: row-splits per group over the partial rows of norm_stats (N*P for
+// batch, P for instance statistics); 1 = stats_finalize alone. More splits keep many CUs busy.
+int stats_row_splits(const Geom& g, int P, bool per_instance) {
+  const int rows = (per_instance ? 1 : g.N) * P;
+  return std::max(1, std::min(32, rows / 16));
+}
+
+// row-splits of sum_partials in norm_bwd_reduce; above 1 they accumulate with atomics, which
+// reorder fp32 sums: single split in deterministic mode
+int bwd_row_splits(int P) {
+  return at::globalContext().deterministicAlgorithms() ? 1 : std::max(1, std::min(16, P / 16));
+}
+
 }  // namespace
 
 // Returns (count[G,C], mean[G,C], var[G,C], scale[G,C], shift[G,C]); scale/shift
@@ -779,8 +792,7 @@ std::vector<at::Tensor> norm_stats(const at::Tensor& x, bool per_instance, doubl
   if (weight.has_value() && weight->defined()) { wf = weight->contiguous().to(at::kFloat); wp = wf.data_ptr<float>(); }
   if (bias.has_value() && bias->defined()) { bf = bias->contiguous().to(at::kFloat); bp = bf.data_ptr<float>(); }
   // two-stage merge: RS row-splits per group keep many CUs busy on the N*P partial rows
-  const int rows = (per_instance ? 1 : g.N) * P;
-  const int RS = std::max(1, std::min(32, rows / 16));
+  const int RS = stats_row_splits(g, P, per_instance);
   const float* mc = pcnt.data_ptr<float>();
   const float* mm = pmean.data_ptr<float>();
   const float* m2p = pm2.data_ptr<float>();
@@ -807,6 +819,30 @@ std::vector<at::Tensor> norm_stats(const at::Tensor& x, bool per_instance, doubl
                      rmp, rvp, nbp, (float)momentum);
   IAMD_LAUNCH_CHECK();
   return {cnt, mean, var, scale, shift, rstd};
+}
+
+// The host-side plan norm_stats (and, for a modulation whose views allow the same vector width,
+// norm_bwd_reduce) takes for x, as name -> value; launches nothing. cl: channels-last kernels;
+// vec: elements per lane; tpr / rpb: threads per pixel row and pixel rows per block (0 for NCHW);
+// nzc: channel blocks (grid z); chunk / P: pixels per chunk and chunks; rs_stats: row-splits of
+// the statistics merge (> 1: stats_merge_rows runs); rs_bwd: row-splits of sum_partials (> 1:
+// atomics; 1 in deterministic mode). For tests: they assert the path a shape is named for.
+py::dict norm_plan(const at::Tensor& x, bool per_instance) {
+  Geom g = geom_of(x);
+  const int vec = pick_vec(g, x.element_size(), {});
+  int P, chunk, tpr, nzc;
+  reduce_plan(g, vec, P, chunk, tpr, nzc);
+  py::dict d;
+  d["cl"] = g.cl;
+  d["vec"] = vec;
+  d["tpr"] = tpr;
+  d["rpb"] = g.cl ? kThreads / tpr : 0;
+  d["nzc"] = nzc;
+  d["chunk"] = chunk;
+  d["P"] = P;
+  d["rs_stats"] = stats_row_splits(g, P, per_instance);
+  d["rs_bwd"] = bwd_row_splits(P);
+  return d;
 }
 
 // Sync-BN merge of the gathered [W, 3, C] (count, mean, var) rows: returns (count, mean, var,
@@ -999,9 +1035,7 @@ std::vector<at::Tensor> norm_bwd_reduce(const at::Tensor& x, const at::Tensor& d
     }
   });
   IAMD_LAUNCH_CHECK();
-  // atomics across row-splits reorder fp32 sums: single split in deterministic mode
-  const int RSs = at::globalContext().deterministicAlgorithms()
-                      ? 1 : std::max(1, std::min(16, P / 16));
+  const int RSs = bwd_row_splits(P);
   auto sums = RSs > 1 ? at::zeros({Q, g.N, g.C}, fopt) : at::empty({Q, g.N, g.C}, fopt);
   hipLaunchKernelGGL(sum_partials, dim3(ceil_div(g.C, 64), g.N, Q * RSs), dim3(64, kFinRows), 0,
                      stream(), ps1, Q, qs, g.N, P, g.C, RSs, sums.data_ptr<float>());
