@@ -88,6 +88,7 @@ at::Tensor resize_nearest_bwd(const at::Tensor& dy, int64_t H, int64_t W, double
 bool stream_capturing();
 void mt_scale(const std::vector<at::Tensor>& xs, const at::Tensor& s);
 at::Tensor mt_sqnorm(const std::vector<at::Tensor>& xs);
+uint64_t mt_table_key(const std::vector<std::vector<at::Tensor>>& lists);
 // correlation.hip (k6 correlation, k8 channelnorm)
 std::vector<at::Tensor> attention_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                       double scale);
@@ -320,6 +321,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("count") = py::none(), py::arg("start") = 0);
   m.def("mt_scale", &iamd::mt_scale, "multi-tensor scale");
   m.def("mt_sqnorm", &iamd::mt_sqnorm, "multi-tensor squared L2 norm");
+  m.def("mt_table_key", &iamd::mt_table_key,
+        "cache key of the device table of up to 5 parallel tensor lists (launches nothing)",
+        py::arg("lists"));
   m.def("mt_l1_loss", &iamd::mt_l1_loss, "multi-tensor weighted L1 loss (k13)");
   m.def("mt_l1_loss_backward", &iamd::mt_l1_loss_backward, "k13 backward");
   m.def("mt_gan_loss", &iamd::mt_gan_loss, "multi-tensor GAN loss over D outputs (k13b)");

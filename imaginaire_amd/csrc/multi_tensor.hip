@@ -140,12 +140,14 @@ uint64_t mix(uint64_t h, uint64_t v) {
   return h;
 }
 
-// Build (or fetch from cache) the device table for up to 5 parallel tensor lists.
-Table& get_table(const std::vector<std::vector<at::Tensor>>& lists, const at::Device& dev) {
+// Cache key of a tensor-list set. It covers everything an entry records: pointers, sizes and
+// the memory layout (a freed tensor's address reused by one of another shape must not hit a
+// stale entry). Every size and stride of list 0 is mixed on its own: folded into one sum, two
+// channels-last weights of equal numel and size(0) met on one key with different
+// (cl_cin, cl_khw).
+uint64_t table_key(const std::vector<std::vector<at::Tensor>>& lists) {
   const size_t T = lists[0].size();
   uint64_t h = 1469598103934665603ULL ^ (uint64_t)lists.size();
-  // the key covers everything an entry records: pointers, sizes and the memory layout (a
-  // freed tensor's address reused by one of another shape must not hit a stale entry)
   for (size_t i = 0; i < T; ++i) {
     for (auto& l : lists) {
       // (an empty tensor stands for "no operand": the optional bf16 shadow of a parameter)
@@ -153,10 +155,19 @@ Table& get_table(const std::vector<std::vector<at::Tensor>>& lists, const at::De
       h = mix(h, (uint64_t)l[i].numel());
     }
     const at::Tensor& t0 = lists[0][i];
-    h = mix(h, t0.dim() > 0 ? (uint64_t)t0.size(0) : 0);
-    h = mix(h, t0.dim() == 4 ? (uint64_t)(t0.size(1) * 31 + t0.size(2) * 7 + t0.size(3)) : 1);
-    h = mix(h, (uint64_t)t0.is_contiguous());
+    h = mix(h, (uint64_t)t0.dim());
+    for (int64_t d = 0; d < t0.dim(); ++d) {
+      h = mix(h, (uint64_t)t0.size(d));
+      h = mix(h, (uint64_t)t0.stride(d));
+    }
   }
+  return h;
+}
+
+// Build (or fetch from cache) the device table for up to 5 parallel tensor lists.
+Table& get_table(const std::vector<std::vector<at::Tensor>>& lists, const at::Device& dev) {
+  const size_t T = lists[0].size();
+  const uint64_t h = table_key(lists);
   std::lock_guard<std::mutex> lk(g_mu);
   auto it = g_cache.find(h);
   if (it != g_cache.end()) {
@@ -253,8 +264,10 @@ adam_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks
     step_size = lr / bc1;
     rbc2 = rsqrtf(bc2);
   }
+  // (the shadow, when there is one, is written 4 bf16 = 8 bytes at a time; null passes)
   const bool vec_ok = (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) % 16 == 0) &&
-                      ((uintptr_t)g % (4 * sizeof(G)) == 0) && (start % 4 == 0);
+                      ((uintptr_t)g % (4 * sizeof(G)) == 0) && ((uintptr_t)shadow % 8 == 0) &&
+                      (start % 4 == 0);
   if (vec_ok) {
     // U groups of 4 elements per lane per trip, all loads issued before any math: 4 x U 16-B
     // loads in flight per lane (one group at a time left the kernel latency-bound at ~1.5 TB/s)
@@ -515,6 +528,14 @@ void check_same_dtype(const std::vector<at::Tensor>& l, at::ScalarType st, const
 }
 
 }  // namespace
+
+// Read-only view of the table cache key for tests: builds, caches and launches nothing.
+uint64_t mt_table_key(const std::vector<std::vector<at::Tensor>>& lists) {
+  IAMD_CHECK(!lists.empty() && lists.size() <= 5, "mt_table_key: 1 to 5 lists");
+  for (auto& l : lists)
+    IAMD_CHECK(l.size() == lists[0].size(), "mt_table_key: list sizes differ");
+  return table_key(lists);
+}
 
 void mt_adam(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
              const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
