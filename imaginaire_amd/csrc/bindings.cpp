@@ -147,6 +147,11 @@ at::Tensor avg_pool_nhwc_fwd(const at::Tensor& x, int64_t kh, int64_t kw, int64_
                              int64_t ph, int64_t pw, bool include_pad);
 at::Tensor avg_pool_nhwc_bwd(const at::Tensor& dy, int64_t H, int64_t W, int64_t kh, int64_t kw,
                              int64_t sh, int64_t sw, int64_t ph, int64_t pw, bool include_pad);
+at::Tensor avg_pool_pad_nhwc_fwd(const at::Tensor& x, int64_t kh, int64_t kw, int64_t sh,
+                                 int64_t sw, int64_t ph, int64_t pw, int64_t pad_mode);
+at::Tensor avg_pool_pad_nhwc_bwd(const at::Tensor& dy, int64_t H, int64_t W, int64_t kh,
+                                 int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                                 int64_t pad_mode);
 // conv_aux.hip
 at::Tensor pad_channels_cast(const at::Tensor& x, int64_t Cp, at::ScalarType dtype);
 void conv_phase_scatter(const at::Tensor& src, at::Tensor& dst, int64_t s, int64_t ry, int64_t rx,
@@ -254,6 +259,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "k14 NHWC max pool backward (argmax recomputed from the input)");
   m.def("avg_pool_nhwc_fwd", &iamd::avg_pool_nhwc_fwd, "NHWC average pooling (k14)");
   m.def("avg_pool_nhwc_bwd", &iamd::avg_pool_nhwc_bwd, "k14 backward (gather)");
+  m.def("avg_pool_pad_nhwc_fwd", &iamd::avg_pool_pad_nhwc_fwd,
+        "k14 over reflect (1) / replicate (2) padding read in place");
+  m.def("avg_pool_pad_nhwc_bwd", &iamd::avg_pool_pad_nhwc_bwd,
+        "k14 backward (gather) through reflect / replicate padding");
   m.def("pad_nhwc_fwd", &iamd::pad_nhwc_fwd, "NHWC reflect / replicate padding");
   m.def("pad_nhwc_bwd", &iamd::pad_nhwc_bwd, "NHWC reflect / replicate padding backward (gather)");
   m.def("conv_weight_flip_t", &iamd::conv_weight_flip_t,

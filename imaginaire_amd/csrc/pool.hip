@@ -208,6 +208,141 @@ PoolGeom geom(const at::Tensor& x, int64_t Ho, int64_t Wo, int64_t kh, int64_t k
   return g;
 }
 
+// k14 with the reflect / replicate padding read in place: y = avg_pool(pad(x, (pw, pw, ph, ph),
+// mode), k, s, padding 0) without the padded copy (FUNIT's ReflectionPad2d(1), AvgPool2d(3, 2)
+// downsamplers). ``pmode`` is pad_map's (common.h: 1 reflect, 2 replicate); g.ph / g.pw are the
+// pad widths, g.Ho / g.Wo the output of the PADDED extent. Every window lies inside that extent,
+// so the divisor is kh * kw everywhere. Same thread mapping as the kernels above.
+template <typename T, int V>
+__global__ void __launch_bounds__(kT)
+avgpool_pad_fwd(const T* __restrict__ x, T* __restrict__ y, PoolGeom g, int pmode) {
+  const int cv = g.C / V;
+  const int64_t total = (int64_t)g.B * g.Ho * g.Wo * cv;
+  const float inv = 1.f / (float)(g.kh * g.kw);
+  for (int64_t t = (int64_t)blockIdx.x * kT + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * kT) {
+    const int c8 = (int)(t % cv);
+    int64_t p = t / cv;
+    const int ox = (int)(p % g.Wo);
+    p /= g.Wo;
+    const int oy = (int)(p % g.Ho);
+    const int b = (int)(p / g.Ho);
+    const int y0 = oy * g.sh - g.ph, x0 = ox * g.sw - g.pw;
+    float acc[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = 0.f;
+    // taps in avgpool_fwd's order: bitwise its result on the explicitly padded copy
+    for (int dy = 0; dy < g.kh; ++dy) {
+      const int iy = pad_map(y0 + dy, g.H, pmode);
+      for (int dx = 0; dx < g.kw; ++dx) {
+        const int ix = pad_map(x0 + dx, g.W, pmode);
+        float v[V];
+        load_vec<T, V>(x + (((int64_t)b * g.H + iy) * g.W + ix) * g.C + c8 * V, v);
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k] += v[k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] *= inv;
+    store_vec<T, V>(y + t * V, acc);
+  }
+}
+
+// Run r (0..2) of the padded coordinates [lo, hi] that read input index i of an axis of n pixels
+// padded by p on both sides (empty: hi < lo). Run 0 is the pixel itself; reflect adds its mirror
+// image about the first pixel (1 <= i <= p) and about the last (n-1-p <= i <= n-2), which a short
+// axis can give both to one pixel; replicate adds the p border copies of the first / last pixel.
+__device__ __forceinline__ void pad_readers(int i, int n, int p, int pmode, int r, int& lo,
+                                            int& hi) {
+  lo = 0;
+  hi = -1;
+  if (r == 0) {
+    lo = hi = i + p;
+  } else if (pmode == 1) {
+    if (r == 1) {
+      if (i >= 1 && i <= p) lo = hi = p - i;
+    } else if (i >= n - 1 - p && i <= n - 2) {
+      lo = hi = p + 2 * (n - 1) - i;
+    }
+  } else if (r == 1) {
+    if (i == 0) hi = p - 1;
+  } else if (i == n - 1) {
+    lo = n + p;
+    hi = n + 2 * p - 1;
+  }
+}
+
+// Gather backward of avgpool_pad_fwd: one thread per (input pixel, V channels) sums dy / (kh*kw)
+// over every output window that holds one of the padded coordinates reading this pixel, in fp32,
+// and stores once (pad-then-pool rounds the padded gradient before folding it).
+template <typename T, int V>
+__global__ void __launch_bounds__(kT)
+avgpool_pad_bwd(const T* __restrict__ dy, T* __restrict__ dx, PoolGeom g, int pmode) {
+  const int cv = g.C / V;
+  const int64_t total = (int64_t)g.B * g.H * g.W * cv;
+  const float inv = 1.f / (float)(g.kh * g.kw);
+  for (int64_t t = (int64_t)blockIdx.x * kT + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * kT) {
+    const int c8 = (int)(t % cv);
+    int64_t p = t / cv;
+    const int ix = (int)(p % g.W);
+    p /= g.W;
+    const int iy = (int)(p % g.H);
+    const int b = (int)(p / g.H);
+    float acc[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = 0.f;
+    for (int ry = 0; ry < 3; ++ry) {
+      int py_lo, py_hi;
+      pad_readers(iy, g.H, g.ph, pmode, ry, py_lo, py_hi);
+      for (int py = py_lo; py <= py_hi; ++py) {
+        // output rows whose window [oy*sh, oy*sh + kh) of the padded extent contains py
+        const int oy_lo = max(0, (py - g.kh + g.sh) / g.sh);
+        const int oy_hi = min(g.Ho - 1, py / g.sh);
+        for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+          if (py < oy * g.sh || py >= oy * g.sh + g.kh) continue;
+          for (int rx = 0; rx < 3; ++rx) {
+            int px_lo, px_hi;
+            pad_readers(ix, g.W, g.pw, pmode, rx, px_lo, px_hi);
+            for (int px = px_lo; px <= px_hi; ++px) {
+              const int ox_lo = max(0, (px - g.kw + g.sw) / g.sw);
+              const int ox_hi = min(g.Wo - 1, px / g.sw);
+              for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+                if (px < ox * g.sw || px >= ox * g.sw + g.kw) continue;
+                float v[V];
+                load_vec<T, V>(dy + (((int64_t)b * g.Ho + oy) * g.Wo + ox) * g.C + c8 * V, v);
+#pragma unroll
+                for (int k = 0; k < V; ++k) acc[k] += v[k] * inv;
+              }
+            }
+          }
+        }
+      }
+    }
+    store_vec<T, V>(dx + t * V, acc);
+  }
+}
+
+// geometry of the padded pools: x is the UNPADDED [B, C, H, W] tensor
+PoolGeom pad_geom(const at::Tensor& x, int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph,
+                  int64_t pw, int64_t pmode) {
+  const int64_t H = x.size(2), W = x.size(3);
+  IAMD_CHECK(kh >= 1 && kw >= 1 && sh >= 1 && sw >= 1 && ph >= 0 && pw >= 0 && (ph > 0 || pw > 0),
+             "avg_pool_pad_nhwc: bad geometry (kernel / stride >= 1, padding >= 0 and not all 0)");
+  IAMD_CHECK(pmode == 1 || pmode == 2, "avg_pool_pad_nhwc: mode is 1 (reflect) or 2 (replicate)");
+  IAMD_CHECK(pmode != 1 || (ph < H && pw < W),
+             "avg_pool_pad_nhwc: reflect padding must be smaller than the input");
+  IAMD_CHECK(H + 2 * ph >= kh && W + 2 * pw >= kw, "avg_pool_pad_nhwc: window above the padded input");
+  IAMD_CHECK(H + 2 * ph < (1ll << 30) && W + 2 * pw < (1ll << 30) && kh * kw < (1ll << 30),
+             "avg_pool_pad_nhwc: extent too large");
+  PoolGeom g;
+  g.B = (int)x.size(0); g.C = (int)x.size(1); g.H = (int)H; g.W = (int)W;
+  g.Ho = (int)((H + 2 * ph - kh) / sh + 1); g.Wo = (int)((W + 2 * pw - kw) / sw + 1);
+  g.kh = (int)kh; g.kw = (int)kw; g.sh = (int)sh; g.sw = (int)sw;
+  g.ph = (int)ph; g.pw = (int)pw; g.include_pad = true;
+  return g;
+}
+
 }  // namespace
 
 at::Tensor avg_pool_nhwc_fwd(const at::Tensor& x, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
@@ -311,6 +446,60 @@ at::Tensor max_pool_nhwc_bwd(const at::Tensor& x, const at::Tensor& dy, int64_t 
                          reinterpret_cast<const scalar_t*>(x.data_ptr()),
                          reinterpret_cast<const scalar_t*>(dy.data_ptr()),
                          reinterpret_cast<scalar_t*>(dx.data_ptr()), g);
+  });
+  IAMD_LAUNCH_CHECK();
+  return dx;
+}
+
+// y = avg_pool(pad(x, (pw, pw, ph, ph), mode), k, s): pad_mode 1 reflect, 2 replicate
+at::Tensor avg_pool_pad_nhwc_fwd(const at::Tensor& x, int64_t kh, int64_t kw, int64_t sh,
+                                 int64_t sw, int64_t ph, int64_t pw, int64_t pad_mode) {
+  IAMD_CHECK(x.is_cuda() && x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                 (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kFloat),
+             "avg_pool_pad_nhwc_fwd: packed channels-last bf16 / fp32 tensor expected");
+  const PoolGeom g = pad_geom(x, kh, kw, sh, sw, ph, pw, pad_mode);
+  auto y = at::empty({g.B, g.C, g.Ho, g.Wo}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const bool v8 = g.C % 8 == 0;
+  const int64_t n = (int64_t)g.B * g.Ho * g.Wo * (v8 ? g.C / 8 : g.C);
+  const int pm = (int)pad_mode;
+  IAMD_DISPATCH_FLOAT_TYPES(x.scalar_type(), "avg_pool_pad_nhwc_fwd", [&] {
+    if (v8)
+      hipLaunchKernelGGL((avgpool_pad_fwd<scalar_t, 8>), dim3(grid_for(n)), dim3(kT), 0, stream(),
+                         reinterpret_cast<const scalar_t*>(x.data_ptr()),
+                         reinterpret_cast<scalar_t*>(y.data_ptr()), g, pm);
+    else
+      hipLaunchKernelGGL((avgpool_pad_fwd<scalar_t, 1>), dim3(grid_for(n)), dim3(kT), 0, stream(),
+                         reinterpret_cast<const scalar_t*>(x.data_ptr()),
+                         reinterpret_cast<scalar_t*>(y.data_ptr()), g, pm);
+  });
+  IAMD_LAUNCH_CHECK();
+  return y;
+}
+
+at::Tensor avg_pool_pad_nhwc_bwd(const at::Tensor& dy, int64_t H, int64_t W, int64_t kh,
+                                 int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                                 int64_t pad_mode) {
+  IAMD_CHECK(dy.is_cuda() && dy.dim() == 4 && dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                 (dy.scalar_type() == at::kBFloat16 || dy.scalar_type() == at::kFloat),
+             "avg_pool_pad_nhwc_bwd: packed channels-last bf16 / fp32 gradient expected");
+  IAMD_CHECK(H >= 1 && W >= 1, "avg_pool_pad_nhwc_bwd: empty input");
+  auto dx = at::empty({dy.size(0), dy.size(1), H, W},
+                      dy.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const PoolGeom g = pad_geom(dx, kh, kw, sh, sw, ph, pw, pad_mode);
+  IAMD_CHECK(dy.size(2) == g.Ho && dy.size(3) == g.Wo,
+             "avg_pool_pad_nhwc_bwd: gradient size does not match the pooled input");
+  const bool v8 = g.C % 8 == 0;
+  const int64_t n = (int64_t)g.B * g.H * g.W * (v8 ? g.C / 8 : g.C);
+  const int pm = (int)pad_mode;
+  IAMD_DISPATCH_FLOAT_TYPES(dy.scalar_type(), "avg_pool_pad_nhwc_bwd", [&] {
+    if (v8)
+      hipLaunchKernelGGL((avgpool_pad_bwd<scalar_t, 8>), dim3(grid_for(n)), dim3(kT), 0, stream(),
+                         reinterpret_cast<const scalar_t*>(dy.data_ptr()),
+                         reinterpret_cast<scalar_t*>(dx.data_ptr()), g, pm);
+    else
+      hipLaunchKernelGGL((avgpool_pad_bwd<scalar_t, 1>), dim3(grid_for(n)), dim3(kT), 0, stream(),
+                         reinterpret_cast<const scalar_t*>(dy.data_ptr()),
+                         reinterpret_cast<scalar_t*>(dx.data_ptr()), g, pm);
   });
   IAMD_LAUNCH_CHECK();
   return dx;
