@@ -2,6 +2,12 @@
 
 Every 2-D convolution issued by the framework's layers goes through here.
 
+**Routing.** :func:`conv2d` and :func:`conv2d_act` normalise their arguments, ask :func:`_route`
+for a :class:`Route` and hand it to :func:`_run`. ``_route`` alone decides, from shapes and dtypes
+(``_tappack_ok`` / ``_tapsplit_ok`` / ``_mfma_ok``, each asked once): tap-pack (thin inputs), else
+tap-split (narrow RGB heads), else k10, else MIOpen. Routes one would not derive afresh are marked
+``QUIRK`` there; ``tests/test_conv_routes_cpu.py`` pins the whole table.
+
 * **MFMA path (k10, ``csrc/conv_mfma.hip``).** bf16 (autocast or bf16 tensors), groups 1,
   Cout % 64 == 0, Cin a multiple of 64 after zero-padding (pad overhead ≤ 1/3), and enough
   output pixels to fill the chip: the forward runs the hand-written implicit-GEMM kernel
@@ -11,7 +17,7 @@ Every 2-D convolution issued by the framework's layers goes through here.
   split-K over pixels) or MIOpen's wrw, whichever was measured faster for the shape (first
   call). The activation backward + bias gradient is the k2 epilogue kernel.
   ``padding_mode='reflect'`` / ``'replicate'``: the k10 / k11 / im2col_pack loaders read the
-  padding pixels of the unpadded activation themselves (``_fused_pad_mode``, ``_FUSED_PAD``);
+  padding pixels of the unpadded activation themselves (``Route.pmode``, ``_FUSED_PAD``);
   only the data gradient is still computed over the padded extent and folded by
   ``pad_nhwc_bwd``. Anything those loaders do not take pads first (``pad``), then convolves.
 * **MIOpen path.** Everything else. MIOpen's fast NHWC solvers require *packed* NHWC
@@ -24,6 +30,7 @@ Every 2-D convolution issued by the framework's layers goes through here.
 
 Reference: the reference's blocks call cuDNN through ``nn.Conv2d`` (layers/conv.py:59-91).
 """
+import collections
 import os
 
 import torch
@@ -110,13 +117,6 @@ def nhwc(t):
     return t
 
 
-def _pad_arg(padding):
-    if isinstance(padding, int):
-        return [padding] * 4
-    ph, pw = padding
-    return [pw, pw, ph, ph]
-
-
 def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(v)
 
@@ -130,6 +130,17 @@ def _out_pad(cout):
     output measured slower than the 64-wide one — the A-operand stream, not the wasted MFMA
     columns, bounds those convs; profiles/spade_step_conv_log_mi355x.txt)."""
     return _round_up(cout, 64)
+
+
+def _stored_channels(c, padded):
+    """The channel count k10 is asked to store (its ``ncv``): the real ``c`` when that is a
+    multiple of 8 (no crop copy afterwards), else the padded width."""
+    return c if (padded != c and c % 8 == 0) else padded
+
+
+def _crop_cast(t, c, dtype):
+    """The first ``c`` channels of ``t``, in ``dtype``."""
+    return (t[:, :c] if t.shape[1] != c else t).to(dtype)
 
 
 def _pad_channels(t, c, dtype=None):
@@ -262,13 +273,23 @@ def _capturing():
     return _GRAPH_ROUTING[0] > 0 or torch.cuda.is_current_stream_capturing()
 
 
+def _native_conv(x, w, groups):
+    """What every hand-written conv path asks of its operands before it looks at sizes."""
+    return x.is_cuda and x.dim() == 4 and w.dim() == 4 and groups == 1 and _mfma_enabled()
+
+
 def mfma_eligible(x, w, stride, padding, dilation, groups):
     """True if the k10 MFMA kernel runs this conv (see module docstring)."""
-    if not (x.is_cuda and x.dim() == 4 and w.dim() == 4 and groups == 1 and _mfma_enabled()):
+    return _native_conv(x, w, groups) and _mfma_ok(
+        tuple(x.shape), tuple(w.shape), _compute_dtype(x, w), stride, padding, dilation)
+
+
+def _mfma_ok(xs, ws, cdt, stride, padding, dilation):
+    # (on plain numbers: input shape [N, C, H, W], weight shape [Cout, Cin, KH, KW], compute dtype)
+    if cdt != torch.bfloat16:
         return False
-    if _compute_dtype(x, w) != torch.bfloat16:
-        return False
-    cout, cin = w.shape[0], w.shape[1]
+    n, h, w_ = xs[0], xs[2], xs[3]
+    cout, cin, kh, kw = ws
     cp, op = _round_up(cin, 64), _out_pad(cout)
     # zero-padded channels cost MFMA work: allow ≤ 1/3 waste, except for the thin RGB-facing
     # convs (3-channel image in / out) where MIOpen's kernels run at ~1 TF/s and a 64-channel
@@ -279,14 +300,13 @@ def mfma_eligible(x, w, stride, padding, dilation, groups):
     if cp * op * 3 > cin * cout * 4 and min(cin, cout) > 16 and cp * op > 2 * cin * cout and \
             not _capturing():  # (in a graph: padded MFMA work rather than MIOpen's backward)
         return False
-    ho, wo = _out_hw(x.shape[2], x.shape[3], w.shape[2:], stride, padding, dilation)
-    if ho <= 0 or wo <= 0 or w.shape[2] * w.shape[3] > 64:  # k10 tap masks are 64-bit
+    ho, wo = _out_hw(h, w_, (kh, kw), stride, padding, dilation)
+    if ho <= 0 or wo <= 0 or kh * kw > 64:  # k10 tap masks are 64-bit
         return False
     # 32-bit buffer byte offsets (k10 < 2 GiB operands, k11 < 1 GiB)
-    if x.shape[0] * cp * x.shape[2] * x.shape[3] * 2 >= (1 << 30) or \
-            x.shape[0] * op * ho * wo * 2 >= (1 << 30):
+    if n * cp * h * w_ * 2 >= (1 << 30) or n * op * ho * wo * 2 >= (1 << 30):
         return False
-    blocks = -(-x.shape[0] * ho * wo // 128) * max(1, op // (128 if op % 128 == 0 else 64))
+    blocks = -(-n * ho * wo // 128) * max(1, op // (128 if op % 128 == 0 else 64))
     # deterministic mode: tiny grids run k10 too (its split-K sums slabs in a fixed order);
     # MIOpen's immediate-mode solvers for them may split K with atomics
     # narrow outputs (flow / mask heads, FlowNet2's predict_flow on 1/64-scale maps): MIOpen
@@ -456,6 +476,20 @@ def _bwd_side_stream():
     return st
 
 
+def _act_bias_bwd(y, dy, slope, need_b, width):
+    """The k10 backwards' first step: the activation backward + bias gradient (k2) at the saved
+    output ``y``'s channel count (the real Cout when k10 stored only those, else the padded one),
+    then dy zero-padded to the GEMMs' ``width`` (without either, ONE pad-cast pass from any dy
+    layout). Returns (padded dy, dy before it, db); at slope 1 the caller sums db from that."""
+    db = None
+    if slope != 1.0:
+        dy = _pad_channels(dy, y.shape[1], torch.bfloat16)
+        dy, db = _ext.ext().bias_act_bwd(y, dy, slope)
+    elif need_b:
+        dy = _pad_channels(dy, dy.shape[1], torch.bfloat16)
+    return _pad_channels(dy, width, torch.bfloat16), dy, db
+
+
 class _MfmaConv2d(torch.autograd.Function):
     """k10 forward / stride-1 dgrad, k11 wgrad, k2 activation + bias backward. Channel
     counts are zero-padded to multiples of 64 (input) / 64 (output) around the kernels.
@@ -488,7 +522,7 @@ class _MfmaConv2d(torch.autograd.Function):
             wb = _pad_rows(_pad_channels(sw.shadow, cp, torch.bfloat16), op)
         ho, wo = _out_hw(x.shape[2], x.shape[3], w.shape[2:], stride, padding, dilation)
         # Cout % 8 == 0: k10 stores only the real output channels (no crop copy after it)
-        ncv = cout if (op != cout and cout % 8 == 0) else op
+        ncv = _stored_channels(cout, op)
         ctx.res_dtype = None if res is None else res.dtype
         ctx.pmode = pmode
         with _Logged('fwd', 'k10', 2.0 * x.shape[0] * ho * wo * op * cp * w.shape[2] * w.shape[3],
@@ -534,10 +568,6 @@ class _MfmaConv2d(torch.autograd.Function):
         if pmode:
             gh, gw = gh + 2 * padding[0], gw + 2 * padding[1]
             padding = (0, 0)
-        # the activation backward runs at the saved output's channel count (the real Cout when
-        # k10 stored only those, else the padded one), then dy is padded for the GEMMs; without
-        # an activation / bias gradient that is ONE pad-cast pass from any dy layout
-        db = None
         # the weight (and, without an activation, the bias) gradient runs on a side stream,
         # concurrently with the data gradient: they are independent, and the small convs'
         # grids leave most CUs idle on their own
@@ -548,13 +578,8 @@ class _MfmaConv2d(torch.autograd.Function):
                  xb.numel() <= _SN_DOT_RATIO * wb.numel())):
             side = None
         side_bias = side is not None and slope == 1.0 and need_b
-        if slope != 1.0:
-            dy = _pad_channels(dy, y.shape[1], torch.bfloat16)
-            dy, db = _ext.ext().bias_act_bwd(y, dy, slope)
-        elif need_b and not side_bias:
-            dy = _pad_channels(dy, dy.shape[1], torch.bfloat16)
-        dy_b = dy  # the bias gradient's operand (identity activation: computed last, below)
-        dy = _pad_channels(dy, wb.shape[0], torch.bfloat16)
+        # (dy_b: the bias gradient's operand; identity activation: computed last, below)
+        dy, dy_b, db = _act_bias_bwd(y, dy, slope, need_b and not side_bias, wb.shape[0])
         dx = dw = None
         cap = _capturing()
         kh, kw = wb.shape[2], wb.shape[3]
@@ -589,7 +614,7 @@ class _MfmaConv2d(torch.autograd.Function):
             fl = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * wb.numel()
             big = dblocks >= _MFMA_MIN_DGRAD_BLOCKS or cap
             # dx keeps only the input's real channels when they are a multiple of 8
-            ncv = xc if (cp != xc and xc % 8 == 0) else cp
+            ncv = _stored_channels(xc, cp)
             if stride == (1, 1) and dilation == (1, 1) and pt[0] >= 0 and pt[1] >= 0 and big:
                 # the flipped weight (made for the whole network in one launch, or cached for a
                 # frozen weight), else one flip_t pass of it here; then the k10 routing (v4 / v5
@@ -629,11 +654,9 @@ class _MfmaConv2d(torch.autograd.Function):
             if pmode:
                 # fold the padded-extent gradient onto the input (the adjoint of the padding),
                 # in the order and dtype the pad-then-conv path folds it
-                if dx.shape[1] != xc:
-                    dx = dx[:, :xc]
                 dx = _ext.ext().pad_nhwc_bwd(
-                    dx.to(xdt).contiguous(memory_format=_CL), xb.shape[2], xb.shape[3], wpad[1],
-                    wpad[1], wpad[0], wpad[0], pmode - 1)
+                    _crop_cast(dx, xc, xdt).contiguous(memory_format=_CL), xb.shape[2],
+                    xb.shape[3], wpad[1], wpad[1], wpad[0], wpad[0], pmode - 1)
             # (fused padding: folding is the adjoint of padding, so <folded dx, x> = <dx, pad(x)>.
             # The fold runs in the input's dtype, as pad-then-conv's does, so for an fp32 input
             # the folded dx is fp32 and <G, W> comes from the k11 epilogue instead)
@@ -643,13 +666,8 @@ class _MfmaConv2d(torch.autograd.Function):
                 # <G, W> = sigma <dx, x> (the adjoint identity): for a low-resolution layer the
                 # activation is smaller than the weight the k11 epilogue would re-read per split
                 sn = tuple(sn) + (_ext.ext().sn_dot_partials(dx, xb, sig),)
-            if dx.shape[1] != xc:
-                dx = dx[:, :xc]
-            dx = dx.to(xdt)
-        elif dx is not None:  # (thin-output path)
-            if dx.shape[1] != xc:
-                dx = dx[:, :xc]
-            dx = dx.to(xdt)
+        if dx is not None:  # (from either path)
+            dx = _crop_cast(dx, xc, xdt)
         if side is not None:
             main.wait_stream(side)
             for t in (dw, db):  # (allocated on the side stream, consumed on this one)
@@ -660,8 +678,6 @@ class _MfmaConv2d(torch.autograd.Function):
                 dest = _take_grad_dest(ctx.wparam, (cout, cin, wb.shape[2], wb.shape[3]))
                 dw = _wgrad(dy, xb, wb, stride, wpad, dilation, cout, cin, wdt, sn, dest,
                             pmode=pmode)
-            elif not need_w_left:  # (thin-output path: already cropped, in fp32)
-                pass
             if dw.shape[0] != cout or dw.shape[1] != cin:
                 dw = dw[:cout, :cin]
             dw = dw.to(wdt)
@@ -711,7 +727,7 @@ def _thin_output_grads(dy, xb, wb, padding, cout, cin, xc, need_x, need_w, wdt):
         # Wd[ci][(t', co)] = w[co, ci, flip(t')]
         wd = torch.zeros((cp, kp), dtype=torch.bfloat16, device=wb.device)
         wd[:, :K] = wb[:cout].flip(2, 3).permute(1, 2, 3, 0).reshape(cp, K)
-        ncv = xc if (cp != xc and xc % 8 == 0) else cp
+        ncv = _stored_channels(xc, cp)
         with _Logged('dgrad', 'k10p', fl, '%s thin-out' % list(dyc.shape)):
             dx = X.conv2d_mfma(dyc, wd.view(cp, kp, 1, 1), None, 1, 1, 0, 0, 1, 1, 1.0, 1, ncv,
                                None, None)
@@ -753,22 +769,6 @@ class SNWeight(object):
         from imaginaire_amd.layers.spectral_norm import _SNScaleCast, materialize_scaled
         w16 = materialize_scaled(self.W, self.sigma, self.shadow)
         return _SNScaleCast.apply(self.W, self.u, self.v, self.sigma, w16, self.shadow)
-
-
-def _sn_fused_ok(x, sw, stride, padding, dilation, residual=None):
-    """The fused SN conv runs exactly where the plain k10 path would (no tap-split head).
-    Decided on the weight's shape alone (a meta tensor: no padded copy of the shadow here)."""
-    cx, cw = x.shape[1], sw.shadow.shape[1]
-    if cx != cw and not (cx == _round_up(cw, 64) and
-                         getattr(x, '_iamd_valid_channels', None) == cw):
-        return False
-    wm = torch.empty((sw.shadow.shape[0], cx) + tuple(sw.shadow.shape[2:]), dtype=torch.bfloat16,
-                     device='meta')
-    if tappack_eligible(_thin_view(x, cw), sw.shadow, stride, padding, dilation, 1) or \
-            tapsplit_eligible(x, wm, stride, padding, dilation, 1) or \
-            not mfma_eligible(x, wm, stride, padding, dilation, 1):
-        return False
-    return residual is None or _residual_fusible(residual, x, wm, stride, padding, dilation)
 
 
 class _MfmaConvPerSample(torch.autograd.Function):
@@ -822,8 +822,7 @@ class _MfmaConvPerSample(torch.autograd.Function):
                 dx = torch.cat([torch.nn.grad.conv2d_input(
                     (1,) + tuple(xs.shape[1:]), ws_[i], dy[i:i + 1].float(), 1, padding,
                     dilation) for i in range(B)])
-                dx = (dx[:, :xc] if dx.shape[1] != xc else dx).to(xdt).contiguous(
-                    memory_format=_CL)
+                dx = _crop_cast(dx, xc, xdt).contiguous(memory_format=_CL)
             if dbg & 2 and ctx.needs_input_grad[1]:
                 g = torch.stack([torch.nn.grad.conv2d_weight(
                     xs[i:i + 1], (op, cp, kh, kw), dy[i:i + 1].float(), 1, padding, dilation)
@@ -834,7 +833,7 @@ class _MfmaConvPerSample(torch.autograd.Function):
             wt = _ext.ext().conv_weight_flip_t(wb, 1, 0, 0, B)
             dx = _ext.ext().conv2d_mfma(dy, wt, None, 1, 1, pt[0], pt[1], dilation[0],
                                         dilation[1], 1.0, B)
-            dx = (dx[:, :xc] if dx.shape[1] != xc else dx).to(xdt)
+            dx = _crop_cast(dx, xc, xdt)
         if ctx.needs_input_grad[1] and dw is None:
             g = _ext.ext().conv2d_wgrad_mfma(dy, xb, kh, kw, 1, 1, padding[0], padding[1],
                                              dilation[0], dilation[1], -1, -1, False, B)
@@ -949,9 +948,9 @@ class _TapSplitConv2d(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             wzt = wz.view(cz, cp).t().contiguous().view(cp, cz, 1, 1)
-            ncv = xc if (cp != xc and xc % 8 == 0) else cp  # only the real input channels
+            ncv = _stored_channels(xc, cp)  # only the real input channels
             dx = _ext.ext().conv2d_mfma(dz, wzt, None, 1, 1, 0, 0, 1, 1, 1.0, 1, ncv)
-            dx = (dx[:, :xc] if dx.shape[1] != xc else dx).to(xdt)
+            dx = _crop_cast(dx, xc, xdt)
         if ctx.needs_input_grad[1]:
             g = _ext.ext().conv2d_wgrad_mfma(dz, xb, 1, 1, 1, 1, 0, 0, 1, 1, cout * kh * kw, cin,
                                              False, 1)
@@ -990,7 +989,7 @@ class _TapPackConv2d(torch.autograd.Function):
                             dilation[0], dilation[1], kp, pmode)
         ctx.pmode = pmode
         wp = _frozen_prep(w, ('tp', kp, op), lambda: _pack_taps(w, kp, op))
-        ncv = cout if (op != cout and cout % 8 == 0) else op
+        ncv = _stored_channels(cout, op)
         with _Logged('fwd', 'k10p', 2.0 * col.shape[0] * col.shape[2] * col.shape[3] * op * kp,
                      _gemm_desc(x, w, stride, padding) + ' tappack'):
             bp = None if bias is None else _frozen_prep(bias, ('b', op),
@@ -1010,14 +1009,9 @@ class _TapPackConv2d(torch.autograd.Function):
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         X = _ext.ext()
         op, kp = wp.shape[0], wp.shape[1]
-        db = None
-        if slope != 1.0:
-            dy = _pad_channels(dy, y.shape[1], torch.bfloat16)
-            dy, db = X.bias_act_bwd(y, dy, slope)
-        elif need_b:
-            dy = _pad_channels(dy, dy.shape[1], torch.bfloat16)
-            db = X.bias_act_bwd(dy, dy, 1.0)[1]
-        dy = _pad_channels(dy, op, torch.bfloat16)
+        dy, dy_b, db = _act_bias_bwd(y, dy, slope, need_b, op)
+        if slope == 1.0 and need_b:
+            db = X.bias_act_bwd(dy_b, dy_b, 1.0)[1]
         dx = dw = None
         pmode, fold = ctx.pmode, None
         if pmode:  # data gradient over the padded extent at padding 0, folded below
@@ -1069,32 +1063,24 @@ class _TapPackConv2d(torch.autograd.Function):
 _TAPPACK = os.environ.get('IMAGINAIRE_AMD_TAPPACK', '1') == '1'
 
 
-def _thin_view(x, cin):
-    """``x`` itself, or — for a channel-padded buffer whose zero tail starts at a thin weight's
-    ``cin`` (``mark_zero_tail``) — the strided view of its real channels, which im2col_pack reads
-    without a copy."""
-    if x.dim() == 4 and x.shape[1] != cin and cin <= 16 and \
-            getattr(x, '_iamd_valid_channels', None) == cin:
-        return x[:, :cin]
-    return x
-
-
 def tappack_eligible(x, w, stride, padding, dilation, groups):
     """The tap-packed path (:class:`_TapPackConv2d`): bf16 compute, groups 1, a thin input
     (Cin <= 16) whose packed K = KH*KW*Cin fits 512, a spatial filter, and enough output pixels
     for the 1x1 GEMM (or inside a graph capture)."""
-    if not (_TAPPACK and x.is_cuda and x.dim() == 4 and w.dim() == 4 and groups == 1 and
-            _mfma_enabled() and x.dtype in (torch.float32, torch.bfloat16)):
+    return _native_conv(x, w, groups) and _tappack_ok(
+        tuple(x.shape), x.dtype, tuple(w.shape), _compute_dtype(x, w), stride, padding, dilation)
+
+
+def _tappack_ok(xs, xdt, ws, cdt, stride, padding, dilation):
+    if not _TAPPACK or xdt not in (torch.float32, torch.bfloat16) or cdt != torch.bfloat16:
         return False
-    cout, cin, kh, kw = w.shape
-    if cin > 16 or x.shape[1] != cin or kh * kw * cin > 512 or kh * kw == 1:
+    cout, cin, kh, kw = ws
+    if cin > 16 or xs[1] != cin or kh * kw * cin > 512 or kh * kw == 1:
         return False
-    if _compute_dtype(x, w) != torch.bfloat16:
-        return False
-    ho, wo = _out_hw(x.shape[2], x.shape[3], (kh, kw), stride, padding, dilation)
+    ho, wo = _out_hw(xs[2], xs[3], (kh, kw), stride, padding, dilation)
     if ho <= 0 or wo <= 0:
         return False
-    m = x.shape[0] * ho * wo
+    m = xs[0] * ho * wo
     kp, op = _round_up(kh * kw * cin, 64), _out_pad(cout)
     # the packed operand is written once and read twice (forward, weight gradient): it pays
     # where it removes >= 8x of the implicit GEMM's zero-padded k loop (RGB / 1-6 channel
@@ -1117,19 +1103,21 @@ _TAPSPLIT = os.environ.get('IMAGINAIRE_AMD_TAPSPLIT', '1') == '1'
 def tapsplit_eligible(x, w, stride, padding, dilation, groups):
     """The tap-split path (``_TapSplitConv2d``) for narrow RGB heads: bf16 compute, stride 1,
     groups 1, Cout <= 8 with a spatial filter, a wide input and enough pixels to fill the chip."""
-    if not (_TAPSPLIT and x.is_cuda and x.dim() == 4 and w.dim() == 4 and groups == 1 and
-            stride == (1, 1) and _mfma_enabled()):
+    return _native_conv(x, w, groups) and _tapsplit_ok(
+        tuple(x.shape), tuple(w.shape), _compute_dtype(x, w), stride, padding, dilation)
+
+
+def _tapsplit_ok(xs, ws, cdt, stride, padding, dilation):
+    if not _TAPSPLIT or stride != (1, 1) or cdt != torch.bfloat16:
         return False
-    cout, cin, kh, kw = w.shape
+    cout, cin, kh, kw = ws
     if not (cout <= 8 and kh * kw > 1 and cin >= 32 and kh * kw * cout <= 512):
         return False
-    if _compute_dtype(x, w) != torch.bfloat16:
+    ho, wo = _out_hw(xs[2], xs[3], (kh, kw), stride, padding, dilation)
+    if (ho, wo) != (xs[2] + 2 * padding[0] - dilation[0] * (kh - 1),
+                    xs[3] + 2 * padding[1] - dilation[1] * (kw - 1)) or ho <= 0 or wo <= 0:
         return False
-    ho, wo = _out_hw(x.shape[2], x.shape[3], (kh, kw), stride, padding, dilation)
-    if (ho, wo) != (x.shape[2] + 2 * padding[0] - dilation[0] * (kh - 1),
-                    x.shape[3] + 2 * padding[1] - dilation[1] * (kw - 1)) or ho <= 0 or wo <= 0:
-        return False
-    npix = x.shape[0] * x.shape[2] * x.shape[3]
+    npix = xs[0] * xs[2] * xs[3]
     cp, cz = _round_up(cin, 64), _round_up(cout * kh * kw, 64)
     # the partials Z must not outweigh the input (MUNIT's 64 -> 3 7x7 head: 147 partial
     # channels per pixel ran slower than the direct 64-wide k10 tile,
@@ -1404,29 +1392,6 @@ def tune_pending():
     return n
 
 
-def conv2d_act(x, weight, bias=None, stride=1, padding=0, dilation=1, slope=1.0):
-    """``act(conv2d(x, weight) + bias)`` with a leaky slope (1 = identity, 0 = relu);
-    one k10 launch when eligible, otherwise MIOpen conv + k2 bias-act epilogue."""
-    stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
-    if isinstance(weight, SNWeight):
-        if _sn_fused_ok(x, weight, stride, padding, dilation):
-            return _MfmaConv2d.apply(x, weight.W, bias, stride, padding, dilation, slope, None,
-                                     weight)
-        weight = weight.materialize()
-    xt = _thin_view(x, weight.shape[1])
-    if tappack_eligible(xt, weight, stride, padding, dilation, 1):
-        return _TapPackConv2d.apply(xt, weight, bias, stride, padding, dilation, slope)
-    weight = _match_channels(x, weight)
-    if slope == 1.0 and tapsplit_eligible(x, weight, stride, padding, dilation, 1):
-        return _TapSplitConv2d.apply(x, weight, bias, padding, dilation)
-    if mfma_eligible(x, weight, stride, padding, dilation, 1):
-        return _MfmaConv2d.apply(x, weight, bias, stride, padding, dilation, slope)
-    from imaginaire_amd.ops.bias_act import bias_act
-    if slope == 1.0:
-        return conv2d(x, weight, bias, stride, padding, dilation)
-    return bias_act(conv2d(x, weight, None, stride, padding, dilation), bias, slope)
-
-
 class _PadNHWC(torch.autograd.Function):
     """Reflect / replicate padding of NHWC activations (csrc/conv_aux.hip pad_nhwc_*)."""
 
@@ -1468,137 +1433,170 @@ _FUSED_PAD = os.environ.get('IMAGINAIRE_AMD_CONV_FUSED_PAD', '1') != '0'
 _FUSED_PAD_MODES = {'reflect': 1, 'replicate': 2}
 
 
-def _fused_pad_mode(x, weight, stride, padding, dilation, groups, padding_mode):
-    """The kernels' padding mode (1 reflect / 2 replicate) when this padded conv can read its
-    padding in place, else 0 (pad-then-conv): symmetric padding within the single-reflection
-    bound, native bf16 compute, Cout > 16 (thin-output heads and tap-split keep the explicit
-    pad), and a conv that reaches :class:`_TapPackConv2d` or :class:`_MfmaConv2d` (k10 then
-    runs the tile the pad-then-conv route would, except that v3 falls to v1). ``weight``
-    is the conv's weight or an :class:`SNWeight` (judged by its bf16 shadow)."""
-    pm = _FUSED_PAD_MODES.get(padding_mode, 0)
-    if isinstance(weight, SNWeight):
-        weight = weight.shadow
-    if not (pm and _FUSED_PAD and groups == 1 and torch.is_tensor(x) and x.is_cuda and
-            x.dim() == 4 and weight.dim() == 4 and _ext.use_native(x) and
-            x.dtype in (torch.bfloat16, torch.float32)):  # (the dtypes pad_nhwc_bwd folds)
-        return 0
+Route = collections.namedtuple('Route', 'kind pmode pad_first res_fused sn_fused thin cpad')
+# kind: 'tappack' | 'tapsplit' | 'k10' | 'miopen'. pmode: 1 reflect / 2 replicate padding read by
+# the loaders themselves (0: none). pad_first: an explicit pad() comes first, the conv then runs at
+# padding 0. res_fused: the residual goes into the k10 epilogue (else added afterwards). sn_fused:
+# an SNWeight is consumed as it is (else materialised). thin: tap-pack reads the real channels of a
+# mark_zero_tail buffer through a view. cpad: MIOpen's operands are zero-padded to this many
+# channels (0: not).
+
+
+def _route(x, weight, stride, padding, dilation, groups=1, padding_mode='zeros', residual=None,
+           slope=1.0):
+    """The :class:`Route` of ``act(conv2d(x, weight), slope) + residual`` (``stride``,
+    ``padding``, ``dilation``: pairs). Pure: it reads shapes, dtypes, layout, the input's
+    ``_iamd_valid_channels``, the module switches and :func:`_capturing`, and launches and
+    allocates nothing. An :class:`SNWeight` is judged by its bf16 shadow (the materialised
+    weight's shape and dtype). Every predicate is asked once, and once more on the padded extent
+    when an explicit pad changes H and W."""
+    sn = isinstance(weight, SNWeight)
+    w = weight.shadow if sn else weight
+    padded = padding_mode not in ('zeros', None)
+    gpu = torch.is_tensor(x) and x.is_cuda and x.dim() == 4
+    # MIOpen's igemm kernels want Cin a multiple of 32 (module docstring)
+    cpad = _round_up(x.shape[1], 32) if (gpu and groups == 1 and x.shape[1] > 64 and
+                                         x.shape[1] % 32) else 0
+    if not (gpu and w.dim() == 4 and groups == 1 and _mfma_enabled()):
+        return Route('miopen', 0, padded, False, False, False, cpad)
+    n, cx, h, wd = x.shape
+    cout, cw, kh, kw = w.shape
     ph, pw = padding
-    cout, cin, kh, kw = weight.shape
-    if ph < 0 or pw < 0 or (ph == 0 and pw == 0) or cout <= 16 or \
-            ph >= x.shape[2] or pw >= x.shape[3] or (pm == 2 and max(ph, pw) >= 15) or \
-            _compute_dtype(x, weight) != torch.bfloat16:
-        return 0
-    if tappack_eligible(_thin_view(x, cin), weight, stride, padding, dilation, 1):
-        return pm
-    cx = x.shape[1]
-    if cx != cin and not (cx == _round_up(cin, 64) and
-                          getattr(x, '_iamd_valid_channels', None) == cin):
-        return 0
-    wm = torch.empty((cout, cx, kh, kw), dtype=torch.bfloat16, device='meta')
-    if tapsplit_eligible(x, wm, stride, padding, dilation, 1) or \
-            not mfma_eligible(x, wm, stride, padding, dilation, 1):
-        return 0
-    return pm
+    cdt = _compute_dtype(x, w)
+    # a mark_zero_tail buffer: _match_channels zero-pads the weight to its width, and tap-pack
+    # reads its real channels through a view when they are few
+    tail = cx > cw and getattr(x, '_iamd_valid_channels', None) == cw
+    thin = tail and cw <= 16
+    wm = (cout, cx, kh, kw) if (cx == cw or tail) else None  # (None: _match_channels raises)
+    # fused padding and the fused SN conv take only a tail that ends at the k10 channel padding
+    tail64 = cx == cw or (tail and cx == _round_up(cw, 64))
+
+    def ask(hh, ww, pd):  # (tap-pack, tap-split, k10) can run an hh x ww map at padding pd
+        return (_tappack_ok((n, cw if thin else cx, hh, ww), x.dtype, (cout, cw, kh, kw), cdt,
+                            stride, pd, dilation),
+                wm is not None and _tapsplit_ok((n, cx, hh, ww), wm, cdt, stride, pd, dilation),
+                wm is not None and _mfma_ok((n, cx, hh, ww), wm, cdt, stride, pd, dilation))
+
+    ho, wo = _out_hw(h, wd, (kh, kw), stride, padding, dilation)
+    # the k10 epilogue can add the residual: bf16 packed NHWC, shaped like the output, whose
+    # channels k10 stores directly (_stored_channels: Cout a multiple of 8)
+    res_ok = residual is not None and _RESIDUAL_EPILOGUE and torch.is_tensor(residual) and \
+        residual.is_cuda and residual.dtype == torch.bfloat16 and residual.dim() == 4 and \
+        residual.is_contiguous(memory_format=_CL) and cout % 8 == 0 and \
+        tuple(residual.shape) == (n, cout, ho, wo)
+    pmode, pad_first = 0, False
+    if padded:
+        # the loaders read the padding in place: within the single-reflection bound, native bf16
+        # compute in a dtype pad_nhwc_bwd folds, Cout > 16 (thin-output heads and tap-split keep
+        # the explicit pad), and a conv that reaches tap-pack or k10. Judged on the UNPADDED
+        # input (k10 then runs the tile the pad-then-conv route would, except that v3 falls to v1)
+        pm = _FUSED_PAD_MODES.get(padding_mode, 0)
+        if pm and _FUSED_PAD and _ext.use_native(x) and \
+                x.dtype in (torch.bfloat16, torch.float32) and \
+                0 <= ph < h and 0 <= pw < wd and (ph or pw) and cout > 16 and \
+                not (pm == 2 and max(ph, pw) >= 15) and cdt == torch.bfloat16:
+            pack, split, k10 = ask(h, wd, padding)
+            if pack or (tail64 and k10 and not split):
+                pmode = pm
+        if pmode and sn and not pack and residual is not None and not res_ok:
+            pmode = 0  # QUIRK: an SN weight whose residual k10 cannot add drops the fused pad too
+        if not pmode:
+            pad_first = True
+            pack, split, k10 = ask(h + 2 * ph, wd + 2 * pw, (0, 0))
+    else:
+        pack, split, k10 = ask(h, wd, padding)
+    direct = k10 and not split  # k10 runs it, were it not for tap-pack
+    if sn and tail64 and direct and not pack and (residual is None or res_ok):
+        # the fused SN conv runs exactly where the plain k10 path would
+        return Route('k10', pmode, pad_first, residual is not None, True, False, 0)
+    res_fused = False
+    if pmode:
+        kind, res_fused = ('tappack', False) if pack else ('k10', res_ok)
+    elif res_ok and direct and (sn or not pad_first):
+        # QUIRK: at zero padding a fusible residual takes k10 without asking tap-pack
+        # QUIRK: after an explicit pad only a materialised SN weight still fuses its residual
+        kind, res_fused = 'k10', True
+    else:
+        kind = 'tappack' if pack else 'tapsplit' if split else 'k10' if k10 else 'miopen'
+    if kind == 'tapsplit' and slope != 1.0 and k10:
+        # conv2d_act takes tap-split only at the identity; where k10 cannot run either, its
+        # conv + bias_act fallback does take it
+        kind = 'k10'
+    return Route(kind, pmode, pad_first, res_fused, False, thin and kind == 'tappack',
+                 cpad if kind == 'miopen' else 0)
 
 
-def _residual_fusible(res, x, weight, stride, padding, dilation):
-    """The k10 epilogue can add ``res`` (a bf16 packed-NHWC tensor shaped like the conv output,
-    whose channels k10 stores directly)."""
-    if res is None or not _RESIDUAL_EPILOGUE or not (
-            torch.is_tensor(res) and res.is_cuda and res.dtype == torch.bfloat16 and
-            res.dim() == 4 and res.is_contiguous(memory_format=_CL)):
-        return False
-    cout = weight.shape[0]
-    op = _out_pad(cout)
-    ncv = cout if (op != cout and cout % 8 == 0) else op
-    ho, wo = _out_hw(x.shape[2], x.shape[3], weight.shape[2:], stride, padding, dilation)
-    return ncv == cout and tuple(res.shape) == (x.shape[0], cout, ho, wo)
+def _run(r, x, weight, bias, stride, padding, dilation, groups, padding_mode, residual, slope):
+    """Execute the :class:`Route` ``r``."""
+    sw = weight if r.sn_fused else None
+
+    def plain(w):
+        return w if not isinstance(w, SNWeight) else w.W if r.sn_fused else w.materialize()
+
+    if not (groups == 1 and x.is_cuda and x.dim() == 4):
+        weight = plain(weight)  # QUIRK: grouped or off the GPU, materialised before the pad
+    if r.pad_first:
+        vc = getattr(x, '_iamd_valid_channels', None)
+        x = pad(nhwc(x), [padding[1]] * 2 + [padding[0]] * 2, padding_mode)
+        if vc is not None:
+            x._iamd_valid_channels = vc
+        padding = (0, 0)
+    weight = plain(weight)
+    # (conv2d_act off the k10 epilogue: the conv, then the k2 bias-act kernel)
+    act_after = slope != 1.0 and r.kind in ('tapsplit', 'miopen')
+    if r.kind == 'tappack':
+        y = _TapPackConv2d.apply(x[:, :weight.shape[1]] if r.thin else x, weight, bias, stride,
+                                 padding, dilation, slope, r.pmode)
+    else:
+        if groups == 1 and sw is None:
+            weight = _match_channels(x, weight)
+        if r.kind == 'k10':
+            y = _MfmaConv2d.apply(nhwc(x) if r.pmode else x, weight, bias, stride, padding,
+                                  dilation, slope, residual if r.res_fused else None, sw, r.pmode)
+        elif r.kind == 'tapsplit':
+            y = _TapSplitConv2d.apply(x, weight, None if act_after else bias, padding, dilation)
+        else:
+            y = _miopen_conv2d(x, weight, None if act_after else bias, stride, padding, dilation,
+                               groups, r.cpad)
+    if act_after:
+        from imaginaire_amd.ops.bias_act import bias_act
+        y = bias_act(y, bias, slope)
+    if residual is not None and not r.res_fused:
+        y = y + residual
+    return y
+
+
+def _miopen_conv2d(x, weight, bias, stride, padding, dilation, groups, cpad):
+    """``F.conv2d``; GPU operands packed channels-last, zero-padded to ``cpad`` channels if set."""
+    if torch.is_tensor(x) and x.is_cuda and x.dim() == 4:
+        if cpad:
+            x = _pad_channels(x, cpad)
+            weight = _pad_channels(weight, cpad)
+        x = nhwc(x)
+        weight = nhwc(weight)
+        if _CONV_LOG is not None and weight.dim() == 4:
+            ho, wo = _out_hw(x.shape[2], x.shape[3], weight.shape[2:], stride, padding, dilation)
+            with _Logged('fwd', 'miopen', 2.0 * x.shape[0] * ho * wo * weight.numel(),
+                         _gemm_desc(x, weight, stride, padding)):
+                return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
+    return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1,
            padding_mode='zeros', residual=None):
     """``F.conv2d`` (+ ``residual``, added to the output: on the k10 path inside its epilogue,
     otherwise as a separate add). ``weight`` may be an :class:`SNWeight`."""
-    if isinstance(weight, SNWeight):
-        st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
-        if groups == 1 and x.is_cuda and x.dim() == 4:
-            pm = 0 if padding_mode in ('zeros', None) else _fused_pad_mode(
-                x, weight, st, pd, dl, groups, padding_mode)
-            if pm and _sn_fused_ok(x, weight, st, pd, dl, residual):
-                # reflect / replicate padding read by the k10 / k11 loaders themselves
-                return _MfmaConv2d.apply(nhwc(x), weight.W, bias, st, pd, dl, 1.0, residual, weight,
-                                         pm)
-            # a thin-input conv takes the materialised weight to the tap-packed path below, which
-            # gathers the padding itself: no explicit pad here
-            thin = pm and tappack_eligible(_thin_view(x, weight.shape[1]), weight.shadow, st, pd,
-                                           dl, 1)
-            if padding_mode not in ('zeros', None) and not thin:
-                # reflect / replicate: pad, then the conv
-                vc = getattr(x, '_iamd_valid_channels', None)
-                x = pad(nhwc(x), _pad_arg(padding), padding_mode)
-                if vc is not None:
-                    x._iamd_valid_channels = vc
-                padding, pd, padding_mode = 0, (0, 0), 'zeros'
-            if _sn_fused_ok(x, weight, st, pd, dl, residual):
-                return _MfmaConv2d.apply(x, weight.W, bias, st, pd, dl, 1.0, residual, weight)
-        weight = weight.materialize()
-    if residual is not None:
-        st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
-        if groups == 1 and padding_mode in ('zeros', None) and x.is_cuda and x.dim() == 4:
-            w = _match_channels(x, weight)
-            if not tapsplit_eligible(x, w, st, pd, dl, groups) and \
-                    mfma_eligible(x, w, st, pd, dl, groups) and \
-                    _residual_fusible(residual, x, w, st, pd, dl):
-                return _MfmaConv2d.apply(x, w, bias, st, pd, dl, 1.0, residual)
-        elif groups == 1 and x.is_cuda and x.dim() == 4 and weight.dim() == 4:
-            # reflect / replicate padding read by the k10 loader: the residual epilogue as well
-            pm = _fused_pad_mode(x, weight, st, pd, dl, groups, padding_mode)
-            if pm and not tappack_eligible(_thin_view(x, weight.shape[1]), weight, st, pd, dl, 1):
-                w = _match_channels(x, weight)
-                if _residual_fusible(residual, x, w, st, pd, dl):
-                    return _MfmaConv2d.apply(nhwc(x), w, bias, st, pd, dl, 1.0, residual, None, pm)
-        return conv2d(x, weight, bias, stride, padding, dilation, groups, padding_mode) + residual
-    if padding_mode != 'zeros' and padding_mode is not None:
-        st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
-        pm = 0 if not (x.is_cuda and x.dim() == 4 and weight.dim() == 4) else _fused_pad_mode(
-            x, weight, st, pd, dl, groups, padding_mode)
-        if pm:  # reflect / replicate padding read by the loaders themselves: no padded copy
-            xt = _thin_view(x, weight.shape[1])
-            if tappack_eligible(xt, weight, st, pd, dl, 1):
-                return _TapPackConv2d.apply(xt, weight, bias, st, pd, dl, 1.0, pm)
-            return _MfmaConv2d.apply(nhwc(x), _match_channels(x, weight), bias, st, pd, dl, 1.0,
-                                     None, None, pm)
-        vc = getattr(x, '_iamd_valid_channels', None)
-        x = pad(nhwc(x), _pad_arg(padding), padding_mode)
-        if vc is not None:
-            x._iamd_valid_channels = vc
-        padding = 0
-    if x.is_cuda and x.dim() == 4 and weight.dim() == 4:
-        st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
-        xt = _thin_view(x, weight.shape[1])
-        if tappack_eligible(xt, weight, st, pd, dl, groups):
-            return _TapPackConv2d.apply(xt, weight, bias, st, pd, dl, 1.0)
-    if groups == 1:
-        weight = _match_channels(x, weight)
-    if x.is_cuda and x.dim() == 4:
-        st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
-        if tapsplit_eligible(x, weight, st, pd, dl, groups):
-            return _TapSplitConv2d.apply(x, weight, bias, pd, dl)
-        if mfma_eligible(x, weight, st, pd, dl, groups):
-            return _MfmaConv2d.apply(x, weight, bias, st, pd, dl, 1.0)
-        cin = weight.shape[1]
-        if groups == 1 and cin > 64 and cin % 32:
-            cp = _round_up(cin, 32)
-            x = _pad_channels(x, cp)
-            weight = _pad_channels(weight, cp)
-        x = nhwc(x)
-        weight = nhwc(weight)
-        if _CONV_LOG is not None and weight.dim() == 4:
-            ho, wo = _out_hw(x.shape[2], x.shape[3], weight.shape[2:], st, pd, dl)
-            with _Logged('fwd', 'miopen', 2.0 * x.shape[0] * ho * wo * weight.numel(),
-                         _gemm_desc(x, weight, st, pd)):
-                return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
-    return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
+    st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
+    return _run(_route(x, weight, st, pd, dl, groups, padding_mode, residual), x, weight, bias,
+                st, pd, dl, groups, padding_mode, residual, 1.0)
+
+
+def conv2d_act(x, weight, bias=None, stride=1, padding=0, dilation=1, slope=1.0):
+    """``act(conv2d(x, weight) + bias)`` with a leaky slope (1 = identity, 0 = relu);
+    one k10 launch when eligible, otherwise the conv + k2 bias-act epilogue."""
+    st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
+    return _run(_route(x, weight, st, pd, dl, slope=slope), x, weight, bias, st, pd, dl, 1,
+                'zeros', None, slope)
 
 
 _DECONV_MIN_PIX = int(os.environ.get('IMAGINAIRE_AMD_DECONV_MIN_PIX', 4096))

@@ -38,7 +38,7 @@ def test_cpu_conv2d_matches_padded_reference(mode, stride, k, p):
 def test_fused_pad_mode_is_zero_off_the_gpu():
     from imaginaire_amd.ops import conv as C
     x, w = torch.randn(1, 64, 8, 8), torch.randn(64, 64, 3, 3)
-    assert C._fused_pad_mode(x, w, (1, 1), (1, 1), (1, 1), 1, 'reflect') == 0
+    assert C._route(x, w, (1, 1), (1, 1), (1, 1), 1, 'reflect').pmode == 0
 
 
 @pytest.mark.parametrize('value,expect', [(None, True), ('0', False)])
