@@ -6,7 +6,10 @@ Every 2-D convolution issued by the framework's layers goes through here.
 for a :class:`Route` and hand it to :func:`_run`. ``_route`` alone decides, from shapes and dtypes
 (``_tappack_ok`` / ``_tapsplit_ok`` / ``_mfma_ok``, each asked once): tap-pack (thin inputs), else
 tap-split (narrow RGB heads), else k10, else MIOpen. Routes one would not derive afresh are marked
-``QUIRK`` there; ``tests/test_conv_routes_cpu.py`` pins the whole table.
+``QUIRK`` there; ``tests/test_conv_routes_cpu.py`` pins the whole table. The k10 and tap-pack
+backwards ask :func:`_bwd_route` in the same way, at backward time, :func:`_dgrad` runs the data
+gradient it names and :func:`_wgrad_choice` picks the weight-gradient kernel
+(``tests/test_conv_bwd_routes_cpu.py``).
 
 * **MFMA path (k10, ``csrc/conv_mfma.hip``).** bf16 (autocast or bf16 tensors), groups 1,
   Cout % 64 == 0, Cin a multiple of 64 after zero-padding (pad overhead ≤ 1/3), and enough
@@ -31,6 +34,7 @@ tap-split (narrow RGB heads), else k10, else MIOpen. Routes one would not derive
 Reference: the reference's blocks call cuDNN through ``nn.Conv2d`` (layers/conv.py:59-91).
 """
 import collections
+import contextlib
 import os
 
 import torch
@@ -464,10 +468,14 @@ _SN_DOT_RATIO = float(os.environ.get('IMAGINAIRE_AMD_SN_DOT_RATIO', '8'))
 _BWD_SIDE = {}
 
 
+def _side_stream_on():
+    return _OVERLAP_BWD in ('1', 'bias', 'small') and _CONV_LOG is None
+
+
 def _bwd_side_stream():
-    """The per-device side stream of the conv backward's weight gradients (None when off, in
-    the conv log's timing mode, or under the eager reference path)."""
-    if _OVERLAP_BWD not in ('1', 'bias', 'small') or _CONV_LOG is not None:
+    """The per-device side stream of the conv backward's weight gradients (None when off or in
+    the conv log's timing mode)."""
+    if not _side_stream_on():
         return None
     dev = torch.cuda.current_device()
     st = _BWD_SIDE.get(dev)
@@ -488,6 +496,159 @@ def _act_bias_bwd(y, dy, slope, need_b, width):
     elif need_b:
         dy = _pad_channels(dy, dy.shape[1], torch.bfloat16)
     return _pad_channels(dy, width, torch.bfloat16), dy, db
+
+
+def _bias_grad(t):
+    """The bias gradient alone: the k2 kernel reads ``t`` and writes no dx."""
+    return _ext.ext().bias_act_bwd(t, t, 1.0)[1]
+
+
+def _finish_grads(dw, db, cout, cin, wdt, bdt, need_b):
+    """The tail of the k10 backwards: (dw, db) cropped to the real channels and cast to the
+    parameters' dtypes; every weight gradient passes the ``_TEST_FLIP_WGRAD`` hook here."""
+    if dw is not None:
+        if dw.shape[0] != cout or dw.shape[1] != cin:
+            dw = dw[:cout, :cin]
+        dw = dw.to(wdt)
+        if _TEST_FLIP_WGRAD[0]:
+            dw = _test_flip_wgrad(dw)
+    if db is not None:
+        db = db[:cout].to(bdt) if need_b else None
+    return dw, db
+
+
+BwdRoute = collections.namedtuple('BwdRoute', 'dgrad gh gw pt ncv fold side side_w db sn_dot')
+# dgrad: 'none' | 'thin' (both gradients from the tap-packed dy, _thin_output_grads) | 'wflip' (k10
+# on the pre-flipped weight) | 'bt' (conv2d_dgrad_mfma: the forward weight, transposed in-kernel) |
+# 'flip' (dilated: k10 on _flip_t of it) | 'k10s' (_strided_dgrad) | 'miopen'. gh, gw: the extent
+# the data gradient is computed over (the padded one under a pad mode, at padding 0); pt: the
+# transposed padding there; ncv: the channels k10 stores. fold: the pad mode (1 reflect / 2
+# replicate) whose pad_nhwc_bwd folds the result onto the input, 0: none. side: the backward forks
+# to the side stream and joins it; side_w: the weight gradient runs there. db: when the bias
+# gradient is computed: 'act' (by the activation backward) | 'side' | 'first' (right after the
+# prologue) | 'last' (after the weight gradient) | 'none'. sn_dot: <G, W> of a spectral-norm weight
+# comes from sigma <dx, x> if the produced dx allows it (the executor's one runtime check).
+
+
+def _bwd_route(dys, xs, ws, stride, padding, dilation, pmode, slope, need_x, need_w, need_b,
+               has_sn, xc, cout, has_wflip, tappack=False):
+    """The :class:`BwdRoute` of a k10 (``tappack``: tap-pack) conv's backward, from the shapes of
+    dy, the saved padded input ``xs`` = [N, cp, H, W] and the k10 weight ``ws`` = [op, cp, KH, KW],
+    the conv's arguments, which gradients are needed, whether the weight is spectrally normalised,
+    the input's real channel count ``xc``, the real ``cout`` and whether a pre-flipped weight
+    exists. Pure, as :func:`_route`: it reads the module switches and :func:`_capturing`, and
+    launches and allocates nothing."""
+    n, cp, kh, kw = dys[0], ws[1], ws[2], ws[3]
+    cap = _capturing()
+    gh, gw = xs[2], xs[3]
+    if pmode:  # over the padded extent at padding 0, exactly as for the conv of a padded copy
+        gh, gw, padding = gh + 2 * padding[0], gw + 2 * padding[1], (0, 0)
+    pt = (dilation[0] * (kh - 1) - padding[0], dilation[1] * (kw - 1) - padding[1])
+    s1, d1 = stride == (1, 1), dilation == (1, 1)
+    inside = 0 <= padding[0] < kh and 0 <= padding[1] < kw
+    phases = stride[0] == stride[1] and 2 <= stride[0] <= 4 and d1
+    # thin OUTPUT (the RGB heads): both gradients from ONE tap-packed operand of dy, instead of
+    # the normal data and weight gradients. QUIRK: never with an SN weight or _TAPPACK off, and
+    # only with the padding (already (0, 0) under a pad mode) inside the kernel
+    thin = not tappack and cout <= 16 and s1 and d1 and not has_sn and _TAPPACK and \
+        kh * kw > 1 and kh * kw * cout <= 512 and inside and (need_x or need_w)
+    # a low-resolution spectral-norm layer: the activation is smaller than the weight the k11
+    # epilogue would re-read per split-K slab
+    sn_small = has_sn and _SN_DOT_RATIO > 0 and \
+        xs[0] * xs[1] * xs[2] * xs[3] <= _SN_DOT_RATIO * (ws[0] * ws[1] * ws[2] * ws[3])
+    # the weight (and, without an activation, the bias) gradient on a side stream, concurrently
+    # with the data gradient: they are independent, and the small convs' grids leave CUs idle
+    # QUIRK: 'small' drops it above _OVERLAP_SMALL_PIX, without a weight gradient, and where the
+    # SN dot shortcut would apply
+    side = not tappack and need_x and (need_w or need_b) and _side_stream_on()
+    if side and _OVERLAP_BWD == 'small' and (n * dys[2] * dys[3] > _OVERLAP_SMALL_PIX or
+                                             not need_w or sn_small):
+        side = False
+    # QUIRK: the fork and join happen even where nothing is left to run on the side stream
+    # ('bias' with an activation, a thin output)
+    side_w = side and need_w and not thin and _OVERLAP_BWD in ('1', 'small')
+    # QUIRK: at the identity k10 sums the bias gradient last, tap-pack first
+    db = 'act' if slope != 1.0 else 'none' if not need_b else 'side' if side else \
+        'first' if tappack else 'last'
+    if thin:
+        kind = 'thin'
+    elif not need_x:
+        kind = 'none'
+    elif tappack:
+        # QUIRK: tap-pack asks for no grid size, no pt >= 0 and no flipped weight at stride 1;
+        # its strided route needs only the padding inside the kernel (neither _STRIDED_DGRAD nor
+        # the size thresholds)
+        kind = 'bt' if (s1 and d1) else 'k10s' if (phases and inside) else 'miopen'
+    else:
+        # the dgrad GEMM has N = Cin (few tiles, K = taps x Cout for the SPADE γ/β convs): k10
+        # splits K over the grid's y dimension for those
+        dblocks = -(-n * gh * gw // 128) * (cp // (128 if cp % 128 == 0 else 64))
+        if s1 and pt[0] >= 0 and pt[1] >= 0 and (dblocks >= _MFMA_MIN_DGRAD_BLOCKS or cap):
+            # QUIRK: the flipped weight was looked up in the forward; without one the stride-1
+            # data gradient reads the forward weight transposed, it makes no fresh flip
+            kind = 'flip' if not d1 else 'wflip' if has_wflip else 'bt'
+        elif _STRIDED_DGRAD and phases and (cap or (
+                dblocks >= _MFMA_MIN_DGRAD_BLOCKS * stride[0] ** 2 and
+                n * gh * gw >= _STRIDED_DGRAD_MIN_PIX)):
+            # large maps only: 1.3-1.6x MIOpen on the full-resolution PatchGAN layers, on par or
+            # slower below ~128K dx pixels (profiles/strided_dgrad_probe_mi355x.txt)
+            kind = 'k10s'
+        else:
+            kind = 'miopen'
+    # QUIRK: the SN dot shortcut only where the weight gradient has not run yet (side stream)
+    runs = kind not in ('none', 'thin')
+    return BwdRoute(kind, gh, gw, pt, _stored_channels(xc, cp), pmode if runs else 0, side,
+                    side_w, db, sn_small and runs and need_w and not side_w)
+
+
+def _dgrad(r, dy, wb, stride, padding, dilation, xc, xdt, sig=None, wflip=None, xb=None,
+           tappack=False):
+    """Run the data gradient of ``r`` (one of 'wflip', 'bt', 'flip', 'k10s', 'miopen') on the
+    padded ``dy`` and the k10 weight ``wb``, 1 / ``sig`` in its epilogue, and fold it under a pad
+    mode. Returns dx with ``r.ncv`` (MIOpen: all) channels, or folded with the real ``xc``."""
+    X = _ext.ext()
+    pd = (0, 0) if r.fold else padding
+    pt, ncv = r.pt, r.ncv
+    tag = ' tappack-in' if tappack else ''
+    fl = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * wb.numel()
+    if r.dgrad in ('wflip', 'flip'):
+        # the flipped weight (made for the whole network in one launch, or cached for a frozen
+        # weight), for a dilated conv one flip_t pass here; then the k10 routing (v4 / v5 for
+        # stride-1 3x3-5x5 rows)
+        wt = wflip if r.dgrad == 'wflip' else _flip_t(wb)
+        with _Logged('dgrad', 'k10', fl, _gemm_desc(dy, wt, (1, 1), pt)):
+            dx = X.conv2d_mfma(dy, wt, None, 1, 1, pt[0], pt[1], dilation[0], dilation[1], 1.0,
+                               1, ncv, None, sig)
+    elif r.dgrad == 'bt':
+        # the forward weight, transposed in-kernel (csrc/conv_mfma.hip dgrad_bt_enabled)
+        # QUIRK: tap-pack's row names the conv's padding, k10's the transposed one
+        with _Logged('dgrad', 'k10', fl, _gemm_desc(dy, wb.transpose(0, 1), (1, 1),
+                                                   pd if tappack else pt) + tag):
+            dx = X.conv2d_dgrad_mfma(dy, wb, pd[0], pd[1], ncv, sig)
+    elif r.dgrad == 'k10s':
+        with _Logged('dgrad', 'k10s', fl, _gemm_desc(dy, wb, stride, pd) + tag):
+            dx = _strided_dgrad(dy, wb, r.gh, r.gw, stride[0], pd, ncv=ncv, ascale=sig)
+    else:
+        # QUIRK: tap-pack's MIOpen fallback writes no conv-log row
+        with contextlib.nullcontext() if tappack else _Logged(
+                'dgrad', 'miopen', fl, _gemm_desc(dy, wb, stride, pd)):
+            # (only the extent's shape is needed: the saved input where it has that shape)
+            xg = xb if (xb is not None and not r.fold) else torch.empty(
+                (dy.shape[0], wb.shape[1], r.gh, r.gw), dtype=torch.bfloat16, device=dy.device,
+                memory_format=_CL)
+            dx = torch.ops.aten.convolution_backward(
+                dy, xg, wb, None, stride, pd, dilation, False, [0, 0], 1,
+                [True, False, False])[0]
+            if sig is not None:
+                dx = dx.div_(sig)  # one pass (fp32 divisor, no reciprocal / cast kernels)
+    if r.fold:
+        # fold the padded-extent gradient onto the input (the adjoint of the padding), in the
+        # order and dtype the pad-then-conv path folds it (QUIRK: cropped, cast and made
+        # channels-last first, on every route)
+        dx = X.pad_nhwc_bwd(_crop_cast(dx, xc, xdt).contiguous(memory_format=_CL),
+                            r.gh - 2 * padding[0], r.gw - 2 * padding[1], padding[1], padding[1],
+                            padding[0], padding[0], r.fold - 1)
+    return dx
 
 
 class _MfmaConv2d(torch.autograd.Function):
@@ -537,6 +698,8 @@ class _MfmaConv2d(torch.autograd.Function):
                     None if bias is None else bias.dtype, x.shape[1])
         ctx.sn = None if sw is None else (sw.shadow, sw.u, sw.v, sig)
         # the weight-gradient destination is looked up on the leaf parameter (DDP bucket slice)
+        # QUIRK: the flipped weight is looked up here, and only for a stride-1 undilated conv whose
+        # input needs a gradient
         ctx.wparam = w if (isinstance(w, torch.nn.Parameter) and w.dtype == torch.float32) else None
         ctx.wflip = _dgrad_weight(wb) if (stride == (1, 1) and dilation == (1, 1) and
                                           ctx.needs_input_grad[0]) else None
@@ -557,138 +720,53 @@ class _MfmaConv2d(torch.autograd.Function):
             _ps_check('conv.dy', dy)
         stride, padding, dilation, slope, cin, cout, xdt, wdt, bdt, xc = ctx.conf
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        sn = ctx.sn
+        sn, pmode = ctx.sn, ctx.pmode
         sig = None if sn is None else sn[3]
-        pmode = ctx.pmode
-        # fused reflect / replicate padding: the data gradient is computed over the padded
-        # extent (gh, gw) at padding 0, exactly as for the conv of a padded copy, and folded
-        # onto the input by pad_nhwc_bwd; the weight gradient is k11 on the unpadded xb
-        wpad = padding
-        gh, gw = xb.shape[2], xb.shape[3]
-        if pmode:
-            gh, gw = gh + 2 * padding[0], gw + 2 * padding[1]
-            padding = (0, 0)
-        # the weight (and, without an activation, the bias) gradient runs on a side stream,
-        # concurrently with the data gradient: they are independent, and the small convs'
-        # grids leave most CUs idle on their own
-        side = _bwd_side_stream() if (need_x and (need_w or need_b)) else None
-        if side is not None and _OVERLAP_BWD == 'small' and (
-                dy.shape[0] * dy.shape[2] * dy.shape[3] > _OVERLAP_SMALL_PIX or not need_w or
-                (sn is not None and _SN_DOT_RATIO > 0 and
-                 xb.numel() <= _SN_DOT_RATIO * wb.numel())):
-            side = None
-        side_bias = side is not None and slope == 1.0 and need_b
-        # (dy_b: the bias gradient's operand; identity activation: computed last, below)
-        dy, dy_b, db = _act_bias_bwd(y, dy, slope, need_b and not side_bias, wb.shape[0])
+        r = _bwd_route(tuple(dy.shape), tuple(xb.shape), tuple(wb.shape), stride, padding,
+                       dilation, pmode, slope, need_x, need_w, need_b, sn is not None, xc, cout,
+                       ctx.wflip is not None)
+        # (dy_b: the bias gradient's operand at the identity activation)
+        dy, dy_b, db = _act_bias_bwd(y, dy, slope, r.db == 'last', wb.shape[0])
         dx = dw = None
-        cap = _capturing()
-        kh, kw = wb.shape[2], wb.shape[3]
-        if cout <= 16 and stride == (1, 1) and dilation == (1, 1) and sn is None and \
-                _TAPPACK and kh * kw > 1 and kh * kw * cout <= 512 and \
-                0 <= padding[0] < kh and 0 <= padding[1] < kw and (need_x or need_w):
-            # thin OUTPUT (the RGB heads): both gradients from ONE tap-packed operand of dy,
+        if r.dgrad == 'thin':
             # dycol[q][(t', co)] = dy[q + t' - (K - 1 - pad)] (t' = flipped tap): dx is the 1x1
             # GEMM of dycol with the flipped weight, dW the 1x1 k11 GEMM of (dycol, x) — no
             # 64-channel padding of dy, no KH*KW x 64 implicit-GEMM k loop over zero channels
             dx, dw = _thin_output_grads(dy[:, :cout], xb, wb, padding, cout, cin, xc, need_x,
                                         need_w, wdt)
-            need_x_left, need_w_left = False, False
-        else:
-            need_x_left, need_w_left = need_x, need_w
-        if side is not None:
-            main = torch.cuda.current_stream()
+        if r.side:
+            main, side = torch.cuda.current_stream(), _bwd_side_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                if side_bias:  # bias gradient only: the k2 kernel reads dy, writes no dx
-                    db = _ext.ext().bias_act_bwd(dy, dy, 1.0)[1]
-                if need_w_left and _OVERLAP_BWD in ('1', 'small'):
-                    dw = _wgrad(dy, xb, wb, stride, wpad, dilation, cout, cin, wdt, sn,
+                if r.db == 'side':
+                    db = _bias_grad(dy)
+                if r.side_w:  # QUIRK: no dest here: this one does not go into the DDP bucket
+                    dw = _wgrad(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn,
                                 pmode=pmode)
-        if need_x_left:
-            pt = (dilation[0] * (kh - 1) - padding[0], dilation[1] * (kw - 1) - padding[1])
-            cp = wb.shape[1]
-            dblocks = -(-dy.shape[0] * gh * gw // 128) * \
-                (cp // (128 if cp % 128 == 0 else 64))
-            # the dgrad GEMM has N = Cin (few tiles, K = taps x Cout for the SPADE γ/β convs):
-            # k10 splits K over the grid's y dimension for those
-            fl = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * wb.numel()
-            big = dblocks >= _MFMA_MIN_DGRAD_BLOCKS or cap
-            # dx keeps only the input's real channels when they are a multiple of 8
-            ncv = _stored_channels(xc, cp)
-            if stride == (1, 1) and dilation == (1, 1) and pt[0] >= 0 and pt[1] >= 0 and big:
-                # the flipped weight (made for the whole network in one launch, or cached for a
-                # frozen weight), else one flip_t pass of it here; then the k10 routing (v4 / v5
-                # for stride-1 3x3-5x5 rows). IMAGINAIRE_AMD_DGRAD_BT=1 reads the forward weight
-                # transposed in-kernel instead (csrc/conv_mfma.hip dgrad_bt_enabled)
-                with _Logged('dgrad', 'k10', fl, _gemm_desc(dy, wb.transpose(0, 1), (1, 1), pt)):
-                    if ctx.wflip is not None:
-                        dx = _ext.ext().conv2d_mfma(dy, ctx.wflip, None, 1, 1, pt[0], pt[1], 1,
-                                                    1, 1.0, 1, ncv, None, sig)
-                    else:
-                        dx = _ext.ext().conv2d_dgrad_mfma(dy, wb, padding[0], padding[1], ncv,
-                                                          sig)
-            elif stride == (1, 1) and pt[0] >= 0 and pt[1] >= 0 and big:
-                wt = _flip_t(wb)
-                with _Logged('dgrad', 'k10', fl, _gemm_desc(dy, wt, (1, 1), pt)):
-                    dx = _ext.ext().conv2d_mfma(dy, wt, None, 1, 1, pt[0], pt[1],
-                                                dilation[0], dilation[1], 1.0, 1, ncv, None, sig)
-            elif _STRIDED_DGRAD and stride[0] == stride[1] and 2 <= stride[0] <= 4 and \
-                    dilation == (1, 1) and (cap or (
-                        dblocks >= _MFMA_MIN_DGRAD_BLOCKS * stride[0] ** 2 and
-                        xb.shape[0] * gh * gw >= _STRIDED_DGRAD_MIN_PIX)):
-                # large maps only: 1.3-1.6x MIOpen on the full-resolution PatchGAN layers, on par
-                # or slower below ~128K dx pixels (profiles/strided_dgrad_probe_mi355x.txt)
-                with _Logged('dgrad', 'k10s', fl, _gemm_desc(dy, wb, stride, padding)):
-                    dx = _strided_dgrad(dy, wb, gh, gw, stride[0], padding, ncv=ncv, ascale=sig)
-            else:
-                with _Logged('dgrad', 'miopen', fl, _gemm_desc(dy, wb, stride, padding)):
-                    # (with fused padding only the padded extent's shape is needed)
-                    xg = xb if not pmode else torch.empty(
-                        (xb.shape[0], xb.shape[1], gh, gw), dtype=xb.dtype, device=xb.device,
-                        memory_format=_CL)
-                    dx = torch.ops.aten.convolution_backward(
-                        dy, xg, wb, None, stride, padding, dilation, False, [0, 0], 1,
-                        [True, False, False])[0]
-                    if sig is not None:
-                        dx = dx.div_(sig)  # one pass (fp32 divisor, no reciprocal / cast kernels)
-            if pmode:
-                # fold the padded-extent gradient onto the input (the adjoint of the padding),
-                # in the order and dtype the pad-then-conv path folds it
-                dx = _ext.ext().pad_nhwc_bwd(
-                    _crop_cast(dx, xc, xdt).contiguous(memory_format=_CL), xb.shape[2],
-                    xb.shape[3], wpad[1], wpad[1], wpad[0], wpad[0], pmode - 1)
+        if r.dgrad not in ('none', 'thin'):
+            dx = _dgrad(r, dy, wb, stride, padding, dilation, xc, xdt, sig, ctx.wflip, xb)
             # (fused padding: folding is the adjoint of padding, so <folded dx, x> = <dx, pad(x)>.
             # The fold runs in the input's dtype, as pad-then-conv's does, so for an fp32 input
             # the folded dx is fp32 and <G, W> comes from the k11 epilogue instead)
-            if sn is not None and need_w and dw is None and _SN_DOT_RATIO > 0 and \
-                    xb.numel() <= _SN_DOT_RATIO * wb.numel() and dx.dtype == torch.bfloat16 and \
-                    dx.shape[1] % 8 == 0 and dx.is_contiguous(memory_format=_CL):
-                # <G, W> = sigma <dx, x> (the adjoint identity): for a low-resolution layer the
-                # activation is smaller than the weight the k11 epilogue would re-read per split
+            # RUNTIME: the one test made on a result. QUIRK: on the folded, not yet cropped dx
+            if r.sn_dot and dx.dtype == torch.bfloat16 and dx.shape[1] % 8 == 0 and \
+                    dx.is_contiguous(memory_format=_CL):
+                # <G, W> = sigma <dx, x> (the adjoint identity)
                 sn = tuple(sn) + (_ext.ext().sn_dot_partials(dx, xb, sig),)
         if dx is not None:  # (from either path)
             dx = _crop_cast(dx, xc, xdt)
-        if side is not None:
+        if r.side:
             main.wait_stream(side)
             for t in (dw, db):  # (allocated on the side stream, consumed on this one)
                 if t is not None:
                     t.record_stream(main)
-        if need_w:
-            if dw is None:
-                dest = _take_grad_dest(ctx.wparam, (cout, cin, wb.shape[2], wb.shape[3]))
-                dw = _wgrad(dy, xb, wb, stride, wpad, dilation, cout, cin, wdt, sn, dest,
-                            pmode=pmode)
-            if dw.shape[0] != cout or dw.shape[1] != cin:
-                dw = dw[:cout, :cin]
-            dw = dw.to(wdt)
-            if _TEST_FLIP_WGRAD[0]:
-                dw = _test_flip_wgrad(dw)
-        if slope == 1.0 and need_b and not side_bias:
-            # identity activation: bias gradient only (the k2 kernel reads dy, writes no dx),
-            # after the data and weight gradients
-            db = _ext.ext().bias_act_bwd(dy_b, dy_b, 1.0)[1]
-        if db is not None:
-            db = db[:cout].to(bdt) if need_b else None
+        if need_w and dw is None:
+            dest = _take_grad_dest(ctx.wparam, (cout, cin, wb.shape[2], wb.shape[3]))
+            dw = _wgrad(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn, dest,
+                        pmode=pmode)
+        if r.db == 'last':  # after the data and weight gradients
+            db = _bias_grad(dy_b)
+        dw, db = _finish_grads(dw, db, cout, cin, wdt, bdt, need_b)
         if _PS_CHECK:
             for nm, t in (('conv.db', db), ('conv.dw', dw), ('conv.dx', dx)):
                 if t is not None:
@@ -735,9 +813,9 @@ def _thin_output_grads(dy, xb, wb, padding, cout, cin, xc, need_x, need_w, wdt):
         with _Logged('wgrad', 'k11', fl, '%s thin-out' % list(dyc.shape)):
             g = X.conv2d_wgrad_mfma(dyc, xb, 1, 1, 1, 1, 0, 0, 1, 1, K, cin, False, 1)
         # g[(t', co)][ci] -> dW[co, ci, t] with t = flip(t')
-        dw = g.reshape(kh, kw, cout, cin).flip(0, 1).permute(2, 3, 0, 1)
-        if _TEST_FLIP_WGRAD[0]:
-            dw = _test_flip_wgrad(dw)
+        # QUIRK: this gradient passes the _TEST_FLIP_WGRAD hook here and again in the caller's tail
+        dw = _finish_grads(g.reshape(kh, kw, cout, cin).flip(0, 1).permute(2, 3, 0, 1), None,
+                           cout, cin, g.dtype, None, False)[0]
     return dx, dw
 
 
@@ -848,8 +926,7 @@ class _MfmaConvPerSample(torch.autograd.Function):
             # per-sample bias gradients on the k2 column-sum kernel (one small launch per
             # sample): torch's dy.sum((2, 3)) came out non-finite from finite dy inside the
             # fs-vid2vid hipGraph replay (scripts/probe/graph_nan_probe.py, PS_CHECK)
-            db = torch.stack([_ext.ext().bias_act_bwd(dy[i:i + 1], dy[i:i + 1], 1.0)[1]
-                              for i in range(B)])[:, :cout].to(bdt)
+            db = torch.stack([_bias_grad(dy[i:i + 1]) for i in range(B)])[:, :cout].to(bdt)
             if _PS_CHECK:
                 _ps_check('db', db)
         if _PS_CHECK and dx is not None:
@@ -958,7 +1035,7 @@ class _TapSplitConv2d(torch.autograd.Function):
             dw = g.reshape(kh, kw, cout, cin).permute(2, 3, 0, 1).to(wdt)
         if ctx.needs_input_grad[2]:  # the k2 column-sum kernel (no torch reduction)
             dyb = nhwc(dy if dy.dtype in (torch.bfloat16, torch.float32) else dy.float())
-            db = _ext.ext().bias_act_bwd(dyb, dyb, 1.0)[1].to(bdt)
+            db = _bias_grad(dyb).to(bdt)
         return dx, dw, db, None, None
 
 
@@ -1009,15 +1086,14 @@ class _TapPackConv2d(torch.autograd.Function):
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         X = _ext.ext()
         op, kp = wp.shape[0], wp.shape[1]
-        dy, dy_b, db = _act_bias_bwd(y, dy, slope, need_b, op)
-        if slope == 1.0 and need_b:
-            db = X.bias_act_bwd(dy_b, dy_b, 1.0)[1]
+        r = _bwd_route(tuple(dy.shape), (dy.shape[0], 64, H, W), (op, 64, kh, kw), stride,
+                       padding, dilation, ctx.pmode, slope, need_x, need_w, need_b, False, cin,
+                       cout, False, tappack=True)
+        dy, dy_b, db = _act_bias_bwd(y, dy, slope, r.db == 'first', op)
+        if r.db == 'first':
+            db = _bias_grad(dy_b)
         dx = dw = None
-        pmode, fold = ctx.pmode, None
-        if pmode:  # data gradient over the padded extent at padding 0, folded below
-            fold = (H, W, padding[1], padding[1], padding[0], padding[0], pmode - 1)
-            H, W, padding = H + 2 * padding[0], W + 2 * padding[1], (0, 0)
-        if need_x:
+        if r.dgrad != 'none':
             # the data gradient of a thin INPUT is a thin-output conv of dy: on the usual k10
             # dgrad (flipped weight, output channels padded to 64). (The adjoint of the packing —
             # a [M][Kp] dcol GEMM + col2im_pack gather — ran at ~12 TF/s: its 2-byte gathers
@@ -1027,36 +1103,15 @@ class _TapPackConv2d(torch.autograd.Function):
                              memory_format=_CL).zero_()
             wb[:cout, :cin] = wp.view(op, kp)[:cout, :K].view(cout, kh, kw, cin).permute(
                 0, 3, 1, 2)
-            fl = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * wb.numel()
-            ncv = cin if cin % 8 == 0 else 64
-            if stride == (1, 1) and dilation == (1, 1):
-                with _Logged('dgrad', 'k10', fl, _gemm_desc(dy, wb.transpose(0, 1), (1, 1),
-                                                           padding) + ' tappack-in'):
-                    dx = X.conv2d_dgrad_mfma(dy, wb, padding[0], padding[1], ncv, None)
-            elif stride[0] == stride[1] and 2 <= stride[0] <= 4 and dilation == (1, 1) and \
-                    0 <= padding[0] < kh and 0 <= padding[1] < kw:
-                with _Logged('dgrad', 'k10s', fl, _gemm_desc(dy, wb, stride, padding) +
-                             ' tappack-in'):
-                    dx = _strided_dgrad(dy, wb, H, W, stride[0], padding, ncv=ncv)
-            else:
-                dx = torch.ops.aten.convolution_backward(
-                    dy, torch.empty((dy.shape[0], 64, H, W), dtype=torch.bfloat16,
-                                    device=dy.device, memory_format=_CL),
-                    wb, None, stride, padding, dilation, False, [0, 0], 1,
-                    [True, False, False])[0]
-            dx = dx[:, :cin].to(xdt)
-            if fold is not None:
-                dx = X.pad_nhwc_bwd(dx.contiguous(memory_format=_CL), *fold)
+            dx = _crop_cast(_dgrad(r, dy, wb, stride, padding, dilation, cin, xdt, tappack=True),
+                            cin, xdt)
         if need_w:
             with _Logged('wgrad', 'k11', 2.0 * col.shape[0] * col.shape[2] * col.shape[3] * op *
                          kp, '%s tappack' % list(col.shape)):
                 g = X.conv2d_wgrad_mfma(dy, col, 1, 1, 1, 1, 0, 0, 1, 1, cout, kh * kw * cin,
                                         False, 1)
-            dw = g.reshape(cout, kh, kw, cin).permute(0, 3, 1, 2).to(wdt)
-            if _TEST_FLIP_WGRAD[0]:
-                dw = _test_flip_wgrad(dw)
-        if db is not None:
-            db = db[:cout].to(bdt) if need_b else None
+            dw = g.reshape(cout, kh, kw, cin).permute(0, 3, 1, 2)
+        dw, db = _finish_grads(dw, db, cout, cin, wdt, bdt, need_b)
         return dx, dw, db, None, None, None, None, None
 
 
@@ -1248,32 +1303,54 @@ def _wgrad(dy, xb, wb, stride, padding, dilation, cout=-1, cin=-1, wdt=torch.flo
     ``xb`` is the unpadded input of a reflect / replicate padded conv (k11 maps the padding)."""
     k11, miopen = _wgrad_fns(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn=sn,
                              dest=dest, pmode=pmode)
-    mode = _MFMA_WGRAD if sn is None else '1'  # (the SN backward rides in k11's split-K sum)
-    fl = 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * wb.numel()
-    desc = _gemm_desc(xb, wb, stride, padding)
-    if mode == '0' and not _capturing():
-        with _Logged('wgrad', 'miopen', fl, desc):
-            return miopen()
-    variants = _k11_variants(dy, xb, wb, stride, dilation, pmode)
-    if mode == '1' and len(variants) == 1:
-        with _Logged('wgrad', 'k11', fl, desc):
-            return k11()
-    # per-shape choice among the candidates (mode 1: the k11 variants; auto: those and MIOpen),
-    # timed by tune_pending() between iterations; the default routing runs until then
-    key = (tuple(dy.shape), tuple(xb.shape), tuple(wb.shape), stride, padding, dilation,
-           cout, cin, wdt) + (() if sn is None else ('sn',) if len(sn) == 4 else ('sndx',)) + \
-        (('pm%d' % pmode,) if pmode else ())
-    # ('sn': tuned with the k11 <G, W> epilogue; 'sndx': <G, W> came from the data gradient)
-    choice = _WGRAD_CHOICE.get(key)
-    if choice is None:
+    mode, cap, has_sn = _MFMA_WGRAD, _capturing(), sn is not None
+    # (k11 is asked for its variants only where the choice can depend on them)
+    variants = _k11_variants(dy, xb, wb, stride, dilation, pmode) \
+        if (mode != '0' or cap or has_sn) else ()
+    key = _wgrad_key(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn, pmode)
+    label, run, pending = _wgrad_choice(key, mode, variants, cap, has_sn)
+    if pending:  # timed by tune_pending() between iterations; the default routing runs until then
         _WGRAD_PENDING.setdefault(key, (dy.dtype, xb.dtype, wb.dtype))
-        choice = 'k11'
-    with _Logged('wgrad', choice, fl, desc):
-        if choice == 'miopen' and sn is None and not _capturing():
-            return miopen()
-        if choice == 'k11v2':
-            return k11(2)
-        return k11(1 if len(variants) > 1 and key in _WGRAD_CHOICE else 0)
+    with _Logged('wgrad', label, 2.0 * dy.shape[0] * dy.shape[2] * dy.shape[3] * wb.numel(),
+                 _gemm_desc(xb, wb, stride, padding)):
+        return miopen() if run == 'miopen' else k11(run)
+
+
+WgradKey = collections.namedtuple('WgradKey',
+                                  'dy x w stride padding dilation cout cin wdt sn pmode')
+# the weight-gradient tuning key: the shapes of dy, the padded input and the k10 weight, the conv's
+# arguments, the real channel counts, the weight's dtype, sn (None | 'sn': tuned with the k11
+# <G, W> epilogue | 'sndx': <G, W> came from the data gradient) and the fused pad mode
+
+
+def _wgrad_key(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn, pmode):
+    return WgradKey(tuple(dy.shape), tuple(xb.shape), tuple(wb.shape), stride, padding, dilation,
+                    cout, cin, wdt, None if sn is None else 'sn' if len(sn) == 4 else 'sndx',
+                    pmode)
+
+
+def _wgrad_choice(key, mode, variants, capturing, has_sn):
+    """(conv-log label, what runs: a k11 variant number or 'miopen', whether the shape is filed
+    for tuning) of the weight gradient ``key`` under ``mode`` (``IMAGINAIRE_AMD_MFMA_WGRAD``),
+    given the k11 ``variants`` that can run it. Pure: it reads ``_WGRAD_CHOICE``."""
+    # QUIRK: an SN weight forces mode '1'; mode '0' and a tuned 'miopen' are ignored with one, and
+    # while capturing
+    if mode == '0' and not capturing and not has_sn:
+        return 'miopen', 'miopen', False
+    if has_sn:
+        mode = '1'
+    if mode == '1' and len(variants) == 1:
+        return 'k11', 0, False
+    # per-shape choice among the candidates (mode 1: the k11 variants; auto: those and MIOpen)
+    choice = _WGRAD_CHOICE.get(key)
+    if choice is None:  # QUIRK: an untuned multi-variant shape runs variant 0
+        return 'k11', 0, True
+    if choice == 'miopen' and not has_sn and not capturing:
+        return 'miopen', 'miopen', False
+    if choice == 'k11v2':
+        return 'k11v2', 2, False
+    # QUIRK: a tuned 'k11' on a multi-variant shape is variant 1 (so is an ignored 'miopen')
+    return choice, 1 if len(variants) > 1 else 0, False
 
 
 def routing_table():
@@ -1346,24 +1423,24 @@ def tune_pending():
     for kind, key, dts in entries:
         if kind == 'w':
             dyt, xt, wt = dts
-            dys, xs, ws, stride, padding, dilation, cout, cin, wdt = key[:9]
-            dy = torch.randn(dys, device=dev).to(dyt).contiguous(memory_format=cl)
-            xb = torch.randn(xs, device=dev).to(xt).contiguous(memory_format=cl)
+            key = WgradKey(*key)
+            ws, cout, cin = key.w, key.cout, key.cin
+            dy = torch.randn(key.dy, device=dev).to(dyt).contiguous(memory_format=cl)
+            xb = torch.randn(key.x, device=dev).to(xt).contiguous(memory_format=cl)
             wb = torch.randn(ws, device=dev).to(wt).contiguous(memory_format=cl)
             sn = None
-            if len(key) > 9 and key[9] == 'sn':  # the k11 variants with their <G, W> epilogue
+            if key.sn == 'sn':  # the k11 variants with their <G, W> epilogue
                 kk = ws[2] * ws[3]
                 sn = (torch.randn((cout, cin) + tuple(ws[2:]), device=dev).to(
                     torch.bfloat16).contiguous(memory_format=cl),
                     torch.randn(cout, device=dev), torch.randn(cin * kk, device=dev),
                     torch.ones(1, device=dev))
-            pm = 1 if 'pm1' in key[9:] else 2 if 'pm2' in key[9:] else 0  # fused padding mode
-            k11, miopen = _wgrad_fns(dy, xb, wb, stride, padding, dilation, cout, cin, wdt,
-                                     sn=sn, pmode=pm)
+            k11, miopen = _wgrad_fns(dy, xb, wb, key.stride, key.padding, key.dilation, cout,
+                                     cin, key.wdt, sn=sn, pmode=key.pmode)
             fns = {}
             if _MFMA_WGRAD != '1' and sn is None:
                 fns['miopen'] = miopen
-            if len(_k11_variants(dy, xb, wb, stride, dilation, pm)) > 1:
+            if len(_k11_variants(dy, xb, wb, key.stride, key.dilation, key.pmode)) > 1:
                 fns['k11'] = lambda: k11(1)
                 fns['k11v2'] = lambda: k11(2)
             else:
@@ -1383,7 +1460,7 @@ def tune_pending():
         t = {c: v for c, v in t.items() if c != '#'}
         choice = min(t, key=t.get)
         if k[0] == 'w':
-            _WGRAD_CHOICE[k[1:]] = choice
+            _WGRAD_CHOICE[WgradKey(*k[1:])] = choice
         else:
             _DECONV_CHOICE[k[1:]] = choice
     n = len(times)
@@ -1626,9 +1703,13 @@ def deconv_eligible(x, weight, stride, padding, output_padding, groups, dilation
     if (min(cin, cout) < 16 and not cap) or kh < s[0] or kw < s[1] or not (
             0 <= padding[0] < kh and 0 <= padding[1] < kw):
         return False
-    ho = (x.shape[2] - 1) * s[0] - 2 * padding[0] + kh
-    wo = (x.shape[3] - 1) * s[1] - 2 * padding[1] + kw
+    ho, wo = _deconv_out_hw(x.shape, weight.shape, s, padding)
     return ho > 0 and wo > 0 and (cap or x.shape[0] * ho * wo >= _DECONV_MIN_PIX)
+
+
+def _deconv_out_hw(xs, ws, stride, padding):
+    return ((xs[2] - 1) * stride[0] - 2 * padding[0] + ws[2],
+            (xs[3] - 1) * stride[1] - 2 * padding[1] + ws[3])
 
 
 def _deconv_phase_weights(weight, s, padding, cp, op, phases=True):
@@ -1677,10 +1758,7 @@ def conv_transpose2d(x, weight, bias=None, stride=1, padding=0, output_padding=0
     phase convolutions of :func:`_strided_dgrad` instead of MIOpen's backward-data solvers."""
     st, pd = _pair(stride), _pair(padding)
     if deconv_eligible(x, weight, st, pd, _pair(output_padding), groups, _pair(dilation)):
-        cin, cout, kh, kw = weight.shape
-        cp, op = _round_up(cin, 64), _out_pad(cout)
-        ho = (x.shape[2] - 1) * st[0] - 2 * pd[0] + kh
-        wo = (x.shape[3] - 1) * st[1] - 2 * pd[1] + kw
+        ho, wo = _deconv_out_hw(x.shape, weight.shape, st, pd)
         xn, wn = nhwc(x), nhwc(weight)
 
         def phase():
@@ -1698,22 +1776,19 @@ def conv_transpose2d(x, weight, bias=None, stride=1, padding=0, output_padding=0
         choice = 'k10s' if _capturing() else (_DECONV_FORCE or _DECONV_CHOICE.get(key))
         if choice is None:
             if key not in _DECONV_PENDING:
-                shapes = (tuple(x.shape), x.dtype, weight.detach(), bias, st, pd)
+                shapes = (tuple(x.shape), x.dtype, weight.detach(), bias)
 
-                def fns(shapes=shapes):
-                    xs, xdt, w, b, st_, pd_ = shapes
+                def fns(shapes=shapes):  # (holds the weight, not the activation)
+                    xs, xdt, w, b = shapes
                     xt = torch.randn(xs, device=w.device).to(xdt)
-                    cin_, cout_, kh_, kw_ = w.shape
-                    ho_ = (xs[2] - 1) * st_[0] - 2 * pd_[0] + kh_
-                    wo_ = (xs[3] - 1) * st_[1] - 2 * pd_[1] + kw_
 
                     def ph():
                         with torch.no_grad():
-                            return _deconv_phase(xt, w, b, st_, pd_, ho_, wo_)
+                            return _deconv_phase(xt, w, b, st, pd, ho, wo)
 
                     def mi():
                         with torch.no_grad():
-                            return F.conv_transpose2d(nhwc(xt), nhwc(w), b, st_, pd_)
+                            return F.conv_transpose2d(nhwc(xt), nhwc(w), b, st, pd)
                     return {'k10s': ph, 'miopen': mi}
                 _DECONV_PENDING[key] = fns
             choice = 'miopen'
