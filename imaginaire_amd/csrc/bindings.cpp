@@ -101,6 +101,8 @@ at::Tensor correlation_forward(const at::Tensor& input1, const at::Tensor& input
 std::vector<at::Tensor> correlation_backward(const at::Tensor& input1, const at::Tensor& input2,
                                              const at::Tensor& grad_out, int64_t pad,
                                              int64_t ks, int64_t md, int64_t s1, int64_t s2);
+py::dict correlation_plan(const at::Tensor& input1, int64_t pad, int64_t ks, int64_t md,
+                          int64_t s1, int64_t s2);
 at::Tensor channelnorm_forward(const at::Tensor& x);
 at::Tensor channelnorm_backward(const at::Tensor& x, const at::Tensor& out,
                                 const at::Tensor& grad_out);
@@ -354,6 +356,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = cat(a, b, zeros) along channels, NHWC (discriminator inputs)");
   m.def("correlation_forward", &iamd::correlation_forward, "FlowNet correlation (k6)");
   m.def("correlation_backward", &iamd::correlation_backward, "k6 backward");
+  m.def("correlation_plan", &iamd::correlation_plan,
+        "host-side route of correlation_forward / correlation_backward for input1 (launches "
+        "nothing): fwd, bwd, s2_template, D, oH, oW, fwd_lds, bwd_lds",
+        py::arg("input1"), py::arg("pad"), py::arg("ks"), py::arg("md"), py::arg("s1"),
+        py::arg("s2"));
   m.def("channelnorm_forward", &iamd::channelnorm_forward, "channel L2 norm (k8)");
   m.def("channelnorm_backward", &iamd::channelnorm_backward, "k8 backward");
 }

@@ -600,17 +600,24 @@ __global__ void chnorm_fwd(const T* __restrict__ x, T* __restrict__ out, int N, 
   out[idx] = from_f<T>(sqrtf(acc));
 }
 
+// The norm is summed again in fp32 (the loop of chnorm_fwd, so the fp32 result is unchanged):
+// a 16-bit saved output would put a second rounding into every gradient element.
 template <typename T>
-__global__ void chnorm_bwd(const T* __restrict__ x, const T* __restrict__ nrm,
-                           const T* __restrict__ g, T* __restrict__ dx, int N, int C, int H,
-                           int W, int64_t sn, int64_t sc, int64_t sh, int64_t sw) {
+__global__ void chnorm_bwd(const T* __restrict__ x, const T* __restrict__ g,
+                           T* __restrict__ dx, int N, int C, int H, int W, int64_t sn,
+                           int64_t sc, int64_t sh, int64_t sw) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)N * H * W) return;
   const int xx = idx % W;
   const int y = (idx / W) % H;
   const int n = idx / ((int64_t)H * W);
   const int64_t off = n * sn + y * sh + xx * sw;
-  const float k = to_f<T>(g[idx]) / (to_f<T>(nrm[idx]) + 1e-9f);
+  float acc = 0.f;
+  for (int c = 0; c < C; ++c) {
+    float v = to_f<T>(x[off + c * sc]);
+    acc += v * v;
+  }
+  const float k = to_f<T>(g[idx]) / (sqrtf(acc) + 1e-9f);
   for (int c = 0; c < C; ++c) dx[off + c * sc] = from_f<T>(to_f<T>(x[off + c * sc]) * k);
 }
 
@@ -620,7 +627,101 @@ inline int corr_out_size(int in, int pad, int ks, int md, int s1) {
   return (int)std::ceil((double)(padded - 2 * border) / (double)s1);
 }
 
+// ---- route planner: which forward / backward kernel a call gets, decided once -------------
+enum class CorrFwd { kMfmaDiag, kMfma, kK1, kGeneric };
+enum class CorrBwd { kK1r, kK1, kElem };
+
+struct CorrPlan {
+  int R, D, oH, oW;
+  CorrFwd fwd;
+  int s2_template;   // S2 of the MFMA instantiation, 0 for the other kernels
+  size_t fwd_lds;    // dynamic LDS bytes of the forward launch
+  CorrBwd bwd;
+  size_t bwd_lds;    // dynamic LDS bytes of the backward launch
+};
+
+inline bool env_not_zero(const char* name) {
+  const char* v = std::getenv(name);
+  return v == nullptr || v[0] != '0';
+}
+
+// a: the first input as the kernels see it ([N, C, H, W]; only its sizes and dtype are read).
+// The three environment switches are read on every call.
+CorrPlan corr_plan(const at::Tensor& a, int64_t pad, int64_t ks, int64_t md, int64_t s1,
+                   int64_t s2) {
+  const int C = a.size(1), H = a.size(2), W = a.size(3);
+  CorrPlan p;
+  p.R = (int)(md / s2);
+  p.D = 2 * p.R + 1;
+  p.oH = corr_out_size(H, pad, ks, md, s1);
+  p.oW = corr_out_size(W, pad, ks, md, s1);
+  const int R = p.R, D = p.D;
+  // ---- forward ----
+  p.s2_template = 0;
+  if (env_not_zero("IMAGINAIRE_AMD_CORR_MFMA") && a.scalar_type() == at::kBFloat16 && ks == 1 &&
+      s1 == 1 && (s2 == 1 || s2 == 2) && C % 32 == 0 && D <= 33 &&
+      (int64_t)H * W * C < (1ll << 31)) {
+    // the diagonal multi-wave kernel (strip staged once per image-2 row) when the strip fits in
+    // LDS; IMAGINAIRE_AMD_CORR_DIAG=0 keeps the one-wave-per-(row, tj) kernel
+    const size_t strip_bytes = (size_t)48 * s2 * (C * 2 + 16);
+    const bool diag = env_not_zero("IMAGINAIRE_AMD_CORR_DIAG") && strip_bytes <= 64 * 1024;
+    p.fwd = diag ? CorrFwd::kMfmaDiag : CorrFwd::kMfma;
+    p.s2_template = (int)s2;
+    p.fwd_lds = diag ? strip_bytes : 0;
+  } else {
+    const int ngrp = kCorrThreads / kTX;
+    const int span = (kTX - 1) * s1 + 2 * R * s2 + 1;
+    const size_t lds = (size_t)span * kLdsPad * sizeof(float);
+    const bool k1 = ks == 1 && D <= ngrp * kMaxDispPerLane && lds <= 96 * 1024;
+    p.fwd = k1 ? CorrFwd::kK1 : CorrFwd::kGeneric;
+    p.fwd_lds = k1 ? lds : 0;
+  }
+  // ---- backward ----
+  const size_t span = (size_t)(kBX + 2 * R * s2);
+  const size_t lds = ((size_t)kBX * D + (span * D + 3) / 4 * 4 + 2 * span * kBCC) * sizeof(float);
+  const char* tb = std::getenv("IMAGINAIRE_AMD_CORR_BWD_TILED");
+  // register-blocked tiled kernel (IMAGINAIRE_AMD_CORR_BWD_TILED=2): measured 0.69-0.86x
+  // corr_bwd_k1 at the FlowNetC shapes (profiles/corr_bwd_probe_mi355x.txt), so not the default
+  const size_t rspan = (size_t)(kRBX + 2 * R * s2);
+  const size_t rlds = ((size_t)kRBX * D + (rspan * D + 3) / 4 * 4) * sizeof(float) +
+                      2 * rspan * kBCC * a.element_size();
+  if (tb != nullptr && tb[0] == '2' && ks == 1 && s1 == 1 && (s2 == 1 || s2 == 2) &&
+      a.element_size() == 2 && C % kBCC == 0 && rlds <= 64 * 1024) {
+    p.bwd = CorrBwd::kK1r;
+    p.bwd_lds = rlds;
+  } else if ((tb == nullptr || tb[0] != '0') && ks == 1 && s1 == 1 && C % kBCC == 0 &&
+             lds <= 96 * 1024) {
+    p.bwd = CorrBwd::kK1;
+    p.bwd_lds = lds;
+  } else {
+    p.bwd = CorrBwd::kElem;
+    p.bwd_lds = 0;
+  }
+  return p;
+}
+
 }  // namespace
+
+// corr_plan as name -> value for the tests (they assert the route a case is named for);
+// launches nothing.
+py::dict correlation_plan(const at::Tensor& input1, int64_t pad, int64_t ks, int64_t md,
+                          int64_t s1, int64_t s2) {
+  IAMD_CHECK(input1.dim() == 4, "correlation: shapes");
+  IAMD_CHECK(ks >= 1 && ks % 2 == 1 && s1 >= 1 && s2 >= 1, "correlation: bad params");
+  const CorrPlan p = corr_plan(input1, pad, ks, md, s1, s2);
+  static const char* const kFwd[] = {"mfma_diag", "mfma", "k1", "generic"};
+  static const char* const kBwd[] = {"k1r", "k1", "elem"};
+  py::dict d;
+  d["fwd"] = kFwd[(int)p.fwd];
+  d["bwd"] = kBwd[(int)p.bwd];
+  d["s2_template"] = p.s2_template;
+  d["D"] = p.D;
+  d["oH"] = p.oH;
+  d["oW"] = p.oW;
+  d["fwd_lds"] = p.fwd_lds;
+  d["bwd_lds"] = p.bwd_lds;
+  return d;
+}
 
 // in1, in2: [N, C, H, W] (any memory format; made channels-last internally)
 // returns [N, D*D, oH, oW] in channels-last memory format, dtype of the inputs.
@@ -631,32 +732,24 @@ at::Tensor correlation_forward(const at::Tensor& input1, const at::Tensor& input
   auto a = input1.contiguous(at::MemoryFormat::ChannelsLast);
   auto b = input2.to(a.scalar_type()).contiguous(at::MemoryFormat::ChannelsLast);
   const int N = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
-  const int R = md / s2, D = 2 * R + 1;
-  const int oH = corr_out_size(H, pad, ks, md, s1), oW = corr_out_size(W, pad, ks, md, s1);
+  const CorrPlan plan = corr_plan(a, pad, ks, md, s1, s2);
+  const int R = plan.R, D = plan.D, oH = plan.oH, oW = plan.oW;
   IAMD_CHECK(oH > 0 && oW > 0, "correlation: empty output");
   auto out = at::empty({N, D * D, oH, oW},
                        a.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int ngrp = kCorrThreads / kTX;
-  const char* mf = std::getenv("IMAGINAIRE_AMD_CORR_MFMA");
-  if ((mf == nullptr || mf[0] != '0') && a.scalar_type() == at::kBFloat16 && ks == 1 && s1 == 1 &&
-      (s2 == 1 || s2 == 2) &&
-      C % 32 == 0 && D <= 33 && (int64_t)H * W * C < (1ll << 31)) {
+  if (plan.fwd == CorrFwd::kMfmaDiag || plan.fwd == CorrFwd::kMfma) {
     auto pa = reinterpret_cast<const __hip_bfloat16*>(a.data_ptr());
     auto pb = reinterpret_cast<const __hip_bfloat16*>(b.data_ptr());
     auto po = reinterpret_cast<__hip_bfloat16*>(out.data_ptr());
-    // the diagonal multi-wave kernel (strip staged once per image-2 row) when the strip fits in
-    // LDS; IMAGINAIRE_AMD_CORR_DIAG=0 keeps the one-wave-per-(row, tj) kernel
-    const char* dg = std::getenv("IMAGINAIRE_AMD_CORR_DIAG");
-    const size_t strip_bytes = (size_t)48 * s2 * (C * 2 + 16);
-    const bool diag = (dg == nullptr || dg[0] != '0') && strip_bytes <= 64 * 1024;
+    const bool diag = plan.fwd == CorrFwd::kMfmaDiag;
     const dim3 gdiag((unsigned)ceil_div(oW, 16 * (int)s2), (unsigned)(oH + 2 * R * (int)s2),
                      (unsigned)N);
     if (diag && s2 == 2)
-      hipLaunchKernelGGL((corr_fwd_mfma_diag<2>), gdiag, dim3(256), strip_bytes, stream(), pa, pb,
-                         po, H, W, C, oH, oW, (int)pad, (int)md, R, D);
+      hipLaunchKernelGGL((corr_fwd_mfma_diag<2>), gdiag, dim3(256), plan.fwd_lds, stream(), pa,
+                         pb, po, H, W, C, oH, oW, (int)pad, (int)md, R, D);
     else if (diag)
-      hipLaunchKernelGGL((corr_fwd_mfma_diag<1>), gdiag, dim3(256), strip_bytes, stream(), pa, pb,
-                         po, H, W, C, oH, oW, (int)pad, (int)md, R, D);
+      hipLaunchKernelGGL((corr_fwd_mfma_diag<1>), gdiag, dim3(256), plan.fwd_lds, stream(), pa,
+                         pb, po, H, W, C, oH, oW, (int)pad, (int)md, R, D);
     else if (s2 == 2)
       hipLaunchKernelGGL((corr_fwd_mfma<2>), dim3(ceil_div(oW, 32), oH, N * D), dim3(64), 0,
                          stream(), pa, pb, po, H, W, C, oH, oW, (int)pad, (int)md, R, D);
@@ -670,12 +763,11 @@ at::Tensor correlation_forward(const at::Tensor& input1, const at::Tensor& input
     auto pa = reinterpret_cast<const scalar_t*>(a.data_ptr());
     auto pb = reinterpret_cast<const scalar_t*>(b.data_ptr());
     auto po = reinterpret_cast<scalar_t*>(out.data_ptr());
-    const int span = (kTX - 1) * s1 + 2 * R * s2 + 1;
-    const size_t lds = (size_t)span * kLdsPad * sizeof(float);
-    if (ks == 1 && D <= ngrp * kMaxDispPerLane && lds <= 96 * 1024) {
+    if (plan.fwd == CorrFwd::kK1) {
       dim3 grid(ceil_div(oW, kTX), oH, N * D);
-      hipLaunchKernelGGL((corr_fwd_k1<scalar_t>), grid, dim3(kCorrThreads), lds, stream(), pa,
-                         pb, po, H, W, C, oH, oW, (int)pad, (int)md, (int)s1, (int)s2, R, D);
+      hipLaunchKernelGGL((corr_fwd_k1<scalar_t>), grid, dim3(kCorrThreads), plan.fwd_lds,
+                         stream(), pa, pb, po, H, W, C, oH, oW, (int)pad, (int)md, (int)s1,
+                         (int)s2, R, D);
     } else {
       dim3 grid(oW, oH, N);
       hipLaunchKernelGGL((corr_fwd_generic<scalar_t>), grid, dim3(kWave), 0, stream(), pa, pb,
@@ -695,8 +787,8 @@ std::vector<at::Tensor> correlation_backward(const at::Tensor& input1, const at:
   auto b = input2.to(a.scalar_type()).contiguous(at::MemoryFormat::ChannelsLast);
   auto g = grad_out.to(at::kFloat).contiguous(at::MemoryFormat::ChannelsLast);
   const int N = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
-  const int R = md / s2, D = 2 * R + 1;
-  const int oH = corr_out_size(H, pad, ks, md, s1), oW = corr_out_size(W, pad, ks, md, s1);
+  const CorrPlan plan = corr_plan(a, pad, ks, md, s1, s2);
+  const int R = plan.R, D = plan.D, oH = plan.oH, oW = plan.oW;
   IAMD_CHECK(g.size(0) == N && g.size(1) == D * D && g.size(2) == oH && g.size(3) == oW,
              "correlation_backward: grad_out shape");
   auto fopt = a.options().dtype(at::kFloat).memory_format(at::MemoryFormat::ChannelsLast);
@@ -704,19 +796,10 @@ std::vector<at::Tensor> correlation_backward(const at::Tensor& input1, const at:
   auto g2 = at::empty({N, C, H, W}, fopt);
   const int64_t total = (int64_t)N * H * W * C;
   if (total == 0) return {g1, g2};
-  const size_t span = (size_t)(kBX + 2 * R * s2);
-  const size_t lds = ((size_t)kBX * D + (span * D + 3) / 4 * 4 + 2 * span * kBCC) * sizeof(float);
-  const char* tb = std::getenv("IMAGINAIRE_AMD_CORR_BWD_TILED");
-  // register-blocked tiled kernel (IMAGINAIRE_AMD_CORR_BWD_TILED=2): measured 0.69-0.86x
-  // corr_bwd_k1 at the FlowNetC shapes (profiles/corr_bwd_probe_mi355x.txt), so not the default
-  const size_t rspan = (size_t)(kRBX + 2 * R * s2);
-  const size_t rlds = ((size_t)kRBX * D + (rspan * D + 3) / 4 * 4) * sizeof(float) +
-                      2 * rspan * kBCC * a.element_size();
-  if (tb != nullptr && tb[0] == '2' && ks == 1 && s1 == 1 && (s2 == 1 || s2 == 2) &&
-      a.element_size() == 2 && C % kBCC == 0 && rlds <= 64 * 1024) {
+  if (plan.bwd == CorrBwd::kK1r) {
     IAMD_DISPATCH_FLOAT_TYPES(a.scalar_type(), "correlation_bwd_k1r", [&] {
       dim3 grid(ceil_div(W, kRBX), H, N * (C / kBCC));
-      hipLaunchKernelGGL((corr_bwd_k1r<scalar_t>), grid, dim3(256), rlds, stream(),
+      hipLaunchKernelGGL((corr_bwd_k1r<scalar_t>), grid, dim3(256), plan.bwd_lds, stream(),
                          reinterpret_cast<const scalar_t*>(a.data_ptr()),
                          reinterpret_cast<const scalar_t*>(b.data_ptr()), g.data_ptr<float>(),
                          g1.data_ptr<float>(), g2.data_ptr<float>(), H, W, C, oH, oW,
@@ -725,11 +808,10 @@ std::vector<at::Tensor> correlation_backward(const at::Tensor& input1, const at:
     IAMD_LAUNCH_CHECK();
     return {g1, g2};
   }
-  if ((tb == nullptr || tb[0] != '0') && ks == 1 && s1 == 1 && C % kBCC == 0 &&
-      lds <= 96 * 1024) {
+  if (plan.bwd == CorrBwd::kK1) {
     IAMD_DISPATCH_FLOAT_TYPES(a.scalar_type(), "correlation_bwd_k1", [&] {
       dim3 grid(ceil_div(W, kBX), H, N * (C / kBCC));
-      hipLaunchKernelGGL((corr_bwd_k1<scalar_t>), grid, dim3(256), lds, stream(),
+      hipLaunchKernelGGL((corr_bwd_k1<scalar_t>), grid, dim3(256), plan.bwd_lds, stream(),
                          reinterpret_cast<const scalar_t*>(a.data_ptr()),
                          reinterpret_cast<const scalar_t*>(b.data_ptr()), g.data_ptr<float>(),
                          g1.data_ptr<float>(), g2.data_ptr<float>(), H, W, C, oH, oW,
@@ -769,7 +851,7 @@ at::Tensor channelnorm_forward(const at::Tensor& x) {
 at::Tensor channelnorm_backward(const at::Tensor& x, const at::Tensor& out,
                                 const at::Tensor& grad_out) {
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  auto nrm = out.to(x.scalar_type()).contiguous();
+  (void)out;  // the kernel sums the norm again in fp32
   auto g = grad_out.to(x.scalar_type()).contiguous();
   auto dx = at::empty_strided(x.sizes(), x.strides(), x.options());
   const int64_t total = (int64_t)N * H * W;
@@ -778,7 +860,6 @@ at::Tensor channelnorm_backward(const at::Tensor& x, const at::Tensor& out,
   IAMD_DISPATCH_FLOAT_TYPES(x.scalar_type(), "channelnorm_bwd", [&] {
     hipLaunchKernelGGL((chnorm_bwd<scalar_t>), dim3(ceil_div(total, 256)), dim3(256), 0, stream(),
                        reinterpret_cast<const scalar_t*>(x.data_ptr()),
-                       reinterpret_cast<const scalar_t*>(nrm.data_ptr()),
                        reinterpret_cast<const scalar_t*>(g.data_ptr()),
                        reinterpret_cast<scalar_t*>(dx.data_ptr()), N, C, H, W, x.stride(0),
                        x.stride(1), x.stride(2), x.stride(3));

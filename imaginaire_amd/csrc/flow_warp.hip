@@ -41,9 +41,9 @@ __device__ __forceinline__ Taps make_taps(float sx, float sy, int H, int W) {
   return t;
 }
 
-template <typename T>
+template <typename T, typename F>
 __global__ void __launch_bounds__(kThreads)
-warp_fwd(const T* __restrict__ img, const T* __restrict__ flow, T* __restrict__ out, int B, int C,
+warp_fwd(const T* __restrict__ img, const F* __restrict__ flow, T* __restrict__ out, int B, int C,
          int H, int W, int64_t isb, int64_t isc, int64_t isy, int64_t isx, int64_t fsb,
          int64_t fsc, int64_t fsy, int64_t fsx, int64_t osb, int64_t osc, int64_t osy,
          int64_t osx) {
@@ -51,8 +51,8 @@ warp_fwd(const T* __restrict__ img, const T* __restrict__ flow, T* __restrict__ 
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * kThreads) {
     const int x = (int)(i % W), y = (int)((i / W) % H), b = (int)(i / ((int64_t)H * W));
-    const T* fp = flow + b * fsb + y * fsy + x * fsx;
-    const float fx = to_f<T>(fp[0]), fy = to_f<T>(fp[fsc]);
+    const F* fp = flow + b * fsb + y * fsy + x * fsx;
+    const float fx = to_f<F>(fp[0]), fy = to_f<F>(fp[fsc]);
     const Taps t = make_taps(x + fx, y + fy, H, W);
     const float w00 = (1.f - t.wx) * (1.f - t.wy), w01 = t.wx * (1.f - t.wy);
     const float w10 = (1.f - t.wx) * t.wy, w11 = t.wx * t.wy;
@@ -69,9 +69,9 @@ warp_fwd(const T* __restrict__ img, const T* __restrict__ flow, T* __restrict__ 
   }
 }
 
-template <typename T>
+template <typename T, typename F>
 __global__ void __launch_bounds__(kThreads)
-warp_bwd(const T* __restrict__ img, const T* __restrict__ flow, const T* __restrict__ dout,
+warp_bwd(const T* __restrict__ img, const F* __restrict__ flow, const T* __restrict__ dout,
          float* __restrict__ dimg, float* __restrict__ dflow, int B, int C, int H, int W,
          int64_t isb, int64_t isc, int64_t isy, int64_t isx, int64_t fsb, int64_t fsc,
          int64_t fsy, int64_t fsx, int64_t dsb, int64_t dsc, int64_t dsy, int64_t dsx) {
@@ -80,8 +80,8 @@ warp_bwd(const T* __restrict__ img, const T* __restrict__ flow, const T* __restr
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * kThreads) {
     const int x = (int)(i % W), y = (int)((i / W) % H), b = (int)(i / ((int64_t)H * W));
-    const T* fp = flow + b * fsb + y * fsy + x * fsx;
-    const float fx = to_f<T>(fp[0]), fy = to_f<T>(fp[fsc]);
+    const F* fp = flow + b * fsb + y * fsy + x * fsx;
+    const float fx = to_f<F>(fp[0]), fy = to_f<F>(fp[fsc]);
     const Taps t = make_taps(x + fx, y + fy, H, W);
     const float w00 = (1.f - t.wx) * (1.f - t.wy), w01 = t.wx * (1.f - t.wy);
     const float w10 = (1.f - t.wx) * t.wy, w11 = t.wx * t.wy;
@@ -116,9 +116,9 @@ warp_bwd(const T* __restrict__ img, const T* __restrict__ flow, const T* __restr
 // ---------------- k7: Resample2d (FlowNet2) -------------------------------
 // Edge-clamped bilinear taps at (x + fx, y + fy); for kernel_size > 1 the
 // reference averages a kernel_size² window of taps around the sample point.
-template <typename T>
+template <typename T, typename F>
 __global__ void __launch_bounds__(kThreads)
-resample2d_fwd(const T* __restrict__ in1, const T* __restrict__ flow, T* __restrict__ out, int B,
+resample2d_fwd(const T* __restrict__ in1, const F* __restrict__ flow, T* __restrict__ out, int B,
                int C, int H, int W, int ks) {
   const int64_t total = (int64_t)B * C * H * W;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < total;
@@ -126,8 +126,8 @@ resample2d_fwd(const T* __restrict__ in1, const T* __restrict__ flow, T* __restr
     const int x = (int)(i % W), y = (int)((i / W) % H);
     const int c = (int)((i / ((int64_t)H * W)) % C), b = (int)(i / ((int64_t)C * H * W));
     const int64_t HW = (int64_t)H * W;
-    const float dx = to_f<T>(flow[(int64_t)b * 2 * HW + (int64_t)y * W + x]);
-    const float dy = to_f<T>(flow[(int64_t)b * 2 * HW + HW + (int64_t)y * W + x]);
+    const float dx = to_f<F>(flow[(int64_t)b * 2 * HW + (int64_t)y * W + x]);
+    const float dy = to_f<F>(flow[(int64_t)b * 2 * HW + HW + (int64_t)y * W + x]);
     const float xf = (float)x + dx, yf = (float)y + dy;
     const float alpha = xf - floorf(xf), beta = yf - floorf(yf);
     const int xL = max(min((int)floorf(xf), W - 1), 0), xR = max(min((int)floorf(xf) + 1, W - 1), 0);
@@ -148,9 +148,9 @@ resample2d_fwd(const T* __restrict__ in1, const T* __restrict__ flow, T* __restr
   }
 }
 
-template <typename T>
+template <typename T, typename F>
 __global__ void __launch_bounds__(kThreads)
-resample2d_bwd(const T* __restrict__ in1, const T* __restrict__ flow, const T* __restrict__ dout,
+resample2d_bwd(const T* __restrict__ in1, const F* __restrict__ flow, const T* __restrict__ dout,
                float* __restrict__ din1, float* __restrict__ dflow, int B, int C, int H, int W,
                int ks) {
   // one thread per (b, y, x): loops channels, accumulates dflow without atomics
@@ -159,8 +159,8 @@ resample2d_bwd(const T* __restrict__ in1, const T* __restrict__ flow, const T* _
        i += (int64_t)gridDim.x * kThreads) {
     const int x = (int)(i % W), y = (int)((i / W) % H), b = (int)(i / ((int64_t)H * W));
     const int64_t HW = (int64_t)H * W;
-    const float dx = to_f<T>(flow[(int64_t)b * 2 * HW + (int64_t)y * W + x]);
-    const float dy = to_f<T>(flow[(int64_t)b * 2 * HW + HW + (int64_t)y * W + x]);
+    const float dx = to_f<F>(flow[(int64_t)b * 2 * HW + (int64_t)y * W + x]);
+    const float dy = to_f<F>(flow[(int64_t)b * 2 * HW + HW + (int64_t)y * W + x]);
     const float xf = (float)x + dx, yf = (float)y + dy;
     const float alpha = xf - floorf(xf), beta = yf - floorf(yf);
     const int xL = max(min((int)floorf(xf), W - 1), 0), xR = max(min((int)floorf(xf) + 1, W - 1), 0);
@@ -195,19 +195,41 @@ int grid_for(int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, 8192));
 }
 
+// The sample position is x + flow in fp32 whatever the image dtype: the kernels read the flow
+// in its own dtype when it is the image's, and as fp32 otherwise (a bf16 image with the fp32
+// flow of FlowNet2 must not move a 50-pixel flow by 0.125 px; 16-bit -> fp32 is exact).
+inline at::Tensor flow_for(const at::Tensor& flow, const at::Tensor& img) {
+  return flow.scalar_type() == img.scalar_type() || flow.scalar_type() == at::kFloat
+             ? flow
+             : flow.to(at::kFloat);
+}
+
+// fn(scalar_t, flow_t) over the image dtype and the dtype flow_for() left the flow in
+#define IAMD_DISPATCH_IMG_FLOW(IMG, FL, NAME, ...)                      \
+  IAMD_DISPATCH_FLOAT_TYPES((IMG).scalar_type(), NAME, [&] {            \
+    if ((FL).scalar_type() == (IMG).scalar_type()) {                    \
+      using flow_t = scalar_t;                                          \
+      __VA_ARGS__();                                                    \
+    } else {                                                            \
+      using flow_t = float;                                             \
+      __VA_ARGS__();                                                    \
+    }                                                                   \
+  })
+
 }  // namespace
 
 at::Tensor flow_warp_fwd(const at::Tensor& img, const at::Tensor& flow) {
   IAMD_CHECK(img.dim() == 4 && flow.dim() == 4 && flow.size(1) == 2, "flow_warp: shapes");
   IAMD_CHECK(img.size(0) == flow.size(0) && img.size(2) == flow.size(2) &&
                  img.size(3) == flow.size(3), "flow_warp: image/flow size mismatch");
-  at::Tensor fl = flow.scalar_type() == img.scalar_type() ? flow : flow.to(img.scalar_type());
+  at::Tensor fl = flow_for(flow, img);
   const int B = img.size(0), C = img.size(1), H = img.size(2), W = img.size(3);
   auto out = at::empty_like(img);
-  IAMD_DISPATCH_FLOAT_TYPES(img.scalar_type(), "flow_warp_fwd", [&] {
-    hipLaunchKernelGGL((warp_fwd<scalar_t>), dim3(grid_for((int64_t)B * H * W)), dim3(kThreads),
-                       0, stream(), reinterpret_cast<const scalar_t*>(img.data_ptr()),
-                       reinterpret_cast<const scalar_t*>(fl.data_ptr()),
+  IAMD_DISPATCH_IMG_FLOW(img, fl, "flow_warp_fwd", [&] {
+    hipLaunchKernelGGL((warp_fwd<scalar_t, flow_t>), dim3(grid_for((int64_t)B * H * W)),
+                       dim3(kThreads), 0, stream(),
+                       reinterpret_cast<const scalar_t*>(img.data_ptr()),
+                       reinterpret_cast<const flow_t*>(fl.data_ptr()),
                        reinterpret_cast<scalar_t*>(out.data_ptr()), B, C, H, W, img.stride(0),
                        img.stride(1), img.stride(2), img.stride(3), fl.stride(0), fl.stride(1),
                        fl.stride(2), fl.stride(3), out.stride(0), out.stride(1), out.stride(2),
@@ -219,16 +241,17 @@ at::Tensor flow_warp_fwd(const at::Tensor& img, const at::Tensor& flow) {
 
 std::vector<at::Tensor> flow_warp_bwd(const at::Tensor& img, const at::Tensor& flow,
                                       const at::Tensor& dout, bool need_dimg) {
-  at::Tensor fl = flow.scalar_type() == img.scalar_type() ? flow : flow.to(img.scalar_type());
+  at::Tensor fl = flow_for(flow, img);
   at::Tensor g = dout.scalar_type() == img.scalar_type() ? dout : dout.to(img.scalar_type());
   const int B = img.size(0), C = img.size(1), H = img.size(2), W = img.size(3);
   auto fopt = img.options().dtype(at::kFloat);
   auto dimg = need_dimg ? at::zeros({B, C, H, W}, fopt) : at::Tensor();
   auto dflow = at::empty({B, 2, H, W}, fopt);
-  IAMD_DISPATCH_FLOAT_TYPES(img.scalar_type(), "flow_warp_bwd", [&] {
-    hipLaunchKernelGGL((warp_bwd<scalar_t>), dim3(grid_for((int64_t)B * H * W)), dim3(kThreads),
-                       0, stream(), reinterpret_cast<const scalar_t*>(img.data_ptr()),
-                       reinterpret_cast<const scalar_t*>(fl.data_ptr()),
+  IAMD_DISPATCH_IMG_FLOW(img, fl, "flow_warp_bwd", [&] {
+    hipLaunchKernelGGL((warp_bwd<scalar_t, flow_t>), dim3(grid_for((int64_t)B * H * W)),
+                       dim3(kThreads), 0, stream(),
+                       reinterpret_cast<const scalar_t*>(img.data_ptr()),
+                       reinterpret_cast<const flow_t*>(fl.data_ptr()),
                        reinterpret_cast<const scalar_t*>(g.data_ptr()),
                        need_dimg ? dimg.data_ptr<float>() : nullptr,
                        dflow.data_ptr<float>(), B, C, H, W, img.stride(0), img.stride(1),
@@ -241,15 +264,16 @@ std::vector<at::Tensor> flow_warp_bwd(const at::Tensor& img, const at::Tensor& f
 
 at::Tensor resample2d_forward(const at::Tensor& in1, const at::Tensor& flow, int64_t ks) {
   auto x = in1.contiguous();
-  auto f = flow.contiguous().to(x.scalar_type());
+  auto f = flow_for(flow, x).contiguous();
   const int B = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   IAMD_CHECK(f.size(0) == B && f.size(1) == 2 && f.size(2) == H && f.size(3) == W,
              "resample2d: flow shape");
   auto out = at::empty_like(x);
-  IAMD_DISPATCH_FLOAT_TYPES(x.scalar_type(), "resample2d_fwd", [&] {
-    hipLaunchKernelGGL((resample2d_fwd<scalar_t>), dim3(grid_for(x.numel())), dim3(kThreads), 0,
-                       stream(), reinterpret_cast<const scalar_t*>(x.data_ptr()),
-                       reinterpret_cast<const scalar_t*>(f.data_ptr()),
+  IAMD_DISPATCH_IMG_FLOW(x, f, "resample2d_fwd", [&] {
+    hipLaunchKernelGGL((resample2d_fwd<scalar_t, flow_t>), dim3(grid_for(x.numel())),
+                       dim3(kThreads), 0, stream(),
+                       reinterpret_cast<const scalar_t*>(x.data_ptr()),
+                       reinterpret_cast<const flow_t*>(f.data_ptr()),
                        reinterpret_cast<scalar_t*>(out.data_ptr()), B, C, H, W, (int)ks);
   });
   IAMD_LAUNCH_CHECK();
@@ -259,17 +283,17 @@ at::Tensor resample2d_forward(const at::Tensor& in1, const at::Tensor& flow, int
 std::vector<at::Tensor> resample2d_backward(const at::Tensor& in1, const at::Tensor& flow,
                                             const at::Tensor& dout, int64_t ks) {
   auto x = in1.contiguous();
-  auto f = flow.contiguous().to(x.scalar_type());
+  auto f = flow_for(flow, x).contiguous();
   auto g = dout.contiguous().to(x.scalar_type());
   const int B = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   auto fopt = x.options().dtype(at::kFloat);
   auto d1 = at::zeros({B, C, H, W}, fopt);
   auto d2 = at::empty({B, 2, H, W}, fopt);
-  IAMD_DISPATCH_FLOAT_TYPES(x.scalar_type(), "resample2d_bwd", [&] {
-    hipLaunchKernelGGL((resample2d_bwd<scalar_t>), dim3(grid_for((int64_t)B * H * W)),
+  IAMD_DISPATCH_IMG_FLOW(x, f, "resample2d_bwd", [&] {
+    hipLaunchKernelGGL((resample2d_bwd<scalar_t, flow_t>), dim3(grid_for((int64_t)B * H * W)),
                        dim3(kThreads), 0, stream(),
                        reinterpret_cast<const scalar_t*>(x.data_ptr()),
-                       reinterpret_cast<const scalar_t*>(f.data_ptr()),
+                       reinterpret_cast<const flow_t*>(f.data_ptr()),
                        reinterpret_cast<const scalar_t*>(g.data_ptr()), d1.data_ptr<float>(),
                        d2.data_ptr<float>(), B, C, H, W, (int)ks);
   });

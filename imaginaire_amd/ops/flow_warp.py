@@ -2,7 +2,9 @@
 
 Same result as the reference ``resample`` (model_utils/fs_vid2vid.py:14-38):
 ``F.grid_sample`` with bilinear interpolation, border padding and
-``align_corners=True`` on a pixel grid shifted by the flow.
+``align_corners=True`` on a pixel grid shifted by the flow. The sample position is formed in
+fp32 from the flow in the flow's own dtype: a bf16 image warped by the fp32 flow of FlowNet2
+keeps the flow's precision.
 """
 import torch
 import torch.nn.functional as F
