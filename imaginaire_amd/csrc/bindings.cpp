@@ -134,6 +134,11 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
                              int64_t nb, int64_t variant,
                              const c10::optional<std::vector<at::Tensor>>& sn,
                              const c10::optional<at::Tensor>& dst, int64_t pad_mode);
+py::dict conv2d_wgrad_plan(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
+                           int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
+                           int64_t out_cout, int64_t out_cin, bool out_bf16, int64_t nb,
+                           int64_t variant, const c10::optional<std::vector<at::Tensor>>& sn,
+                           const c10::optional<at::Tensor>& dst, int64_t pad_mode);
 bool conv2d_wgrad_v2_eligible(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
                               int64_t sh, int64_t sw, int64_t dh, int64_t dw, int64_t nb,
                               int64_t pad_mode);
@@ -231,6 +236,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "sigma * <dx, x> as partial sums: <G, W> of a spectrally normalised conv (k11 SN)",
         py::arg("dx"), py::arg("x"), py::arg("sigma"));
   m.def("conv2d_wgrad_mfma", &iamd::conv2d_wgrad_mfma, "MFMA conv weight gradient (k11)",
+        py::arg("dy"), py::arg("x"), py::arg("KH"), py::arg("KW"), py::arg("sh"), py::arg("sw"),
+        py::arg("ph"), py::arg("pw"), py::arg("dh"), py::arg("dw"), py::arg("out_cout") = -1,
+        py::arg("out_cin") = -1, py::arg("out_bf16") = false, py::arg("nb") = 1,
+        py::arg("variant") = 0, py::arg("sn") = py::none(), py::arg("dst") = py::none(),
+        py::arg("pad_mode") = 0);
+  m.def("conv2d_wgrad_plan", &iamd::conv2d_wgrad_plan,
+        "host-side plan of conv2d_wgrad_mfma for the same arguments (launches nothing): kernel, "
+        "S, tiles, finished_in_kernel, epilogue",
         py::arg("dy"), py::arg("x"), py::arg("KH"), py::arg("KW"), py::arg("sh"), py::arg("sw"),
         py::arg("ph"), py::arg("pw"), py::arg("dh"), py::arg("dw"), py::arg("out_cout") = -1,
         py::arg("out_cin") = -1, py::arg("out_bf16") = false, py::arg("nb") = 1,

@@ -90,6 +90,32 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// Scalars of the spectral-norm weight-gradient formula dW = G / sigma - (<G, W> / sigma^2) u v^T
+// from the <G, W> partial sums dotp[0 .. ndot): summed by every block of T threads itself, in
+// one fixed order (thread-strided, wave shuffle, waves in order). Shared by wgrad_finalize_sn
+// (conv_aux.hip) and the k11 epilogue that writes the finished gradient of a single slab
+// (conv_wgrad_mfma.hip), whose results must agree bit for bit. sh: T / 64 floats of LDS;
+// holds a block barrier.
+struct SnCoef {
+  float inv;  // 1 / sigma
+  float cf;   // <G, W> / sigma^2
+};
+template <int T>
+__device__ __forceinline__ SnCoef sn_coef(const float* __restrict__ dotp, int ndot,
+                                          const float* __restrict__ sigma, float* sh) {
+  const int tid = threadIdx.x;
+  float dd = 0.f;
+  for (int k = tid; k < ndot; k += T) dd += dotp[k];
+  dd = wave_sum(dd);
+  if ((tid & 63) == 0) sh[tid >> 6] = dd;
+  __syncthreads();
+  float dot = 0.f;
+#pragma unroll
+  for (int k = 0; k < T / 64; ++k) dot += sh[k];
+  const float inv = 1.f / sigma[0];
+  return SnCoef{inv, dot * inv * inv};
+}
+
 // Chan et al. parallel merge of (count, mean, M2) triples.
 __device__ __forceinline__ void chan_merge(float& n_a, float& mean_a, float& m2_a, float n_b,
                                            float mean_b, float m2_b) {

@@ -148,16 +148,8 @@ wgrad_finalize_sn_kernel(const float* __restrict__ part, float* __restrict__ out
   __shared__ float dsh[kT / 64];
   const int opb = kT / G;
   const int tid = threadIdx.x, o = tid % opb, g = tid / opb;
-  float dd = 0.f;
-  for (int k = tid; k < ndot; k += kT) dd += dotp[k];
-  dd = wave_sum(dd);
-  if ((tid & 63) == 0) dsh[tid >> 6] = dd;
-  __syncthreads();
-  float dot = 0.f;
-#pragma unroll
-  for (int k = 0; k < kT / 64; ++k) dot += dsh[k];
-  const float inv = 1.f / sigma[0];
-  const float cf = dot * inv * inv;  // <G, W> / sigma^2
+  const SnCoef sc = sn_coef<kT>(dotp, ndot, sigma, dsh);
+  const float inv = sc.inv, cf = sc.cf;  // 1 / sigma, <G, W> / sigma^2
   const int per = VEC ? Cin / 4 : Cin;
   const int64_t n = (int64_t)Cout * KK * per;
   const int64_t slab = (int64_t)Cop * KK * Cip;

@@ -17,10 +17,19 @@
 // touches fall into 8 different 32-byte bank windows: conflict-free. The DMA is
 // buffer_load ... lds: out-of-image input pixels (padding) and the pixel tail get an
 // out-of-range offset and read as zeros; when Wo % 64 == 0 a k-step is one output-row
-// segment and its pixel coordinates are wave-uniform scalars. Partial sums per split are
-// written as fp32 slabs [S][Cout][taps][Cin] and summed by a second, bandwidth-bound kernel
-// that also crops padded channels and casts to the parameter dtype (conv_aux.hip
-// wgrad_finalize); one fp32 uncropped slab (S == 1) is written straight into dW.
+// segment and its pixel coordinates are wave-uniform scalars.
+//
+// Output. With S > 1 splits (or nb > 1 gradients) the partial sums are written as fp32 slabs
+// [S][Cout][taps][Cin] and summed by a second, bandwidth-bound kernel that also crops padded
+// channels, casts to the parameter dtype and applies the spectral-norm backward (conv_aux.hip
+// wgrad_finalize / wgrad_finalize_sn). One slab (S == 1, nb == 1) holds every sum already and
+// is written as the finished dW by this kernel — straight, cropped, cast to bf16, or with the
+// spectral-norm backward when <G, W> is given as partials — with no slab and no second kernel;
+// only the spectral-norm case whose <G, W> comes from this launch's own epilogue (complete
+// after every block has finished) keeps the second pass. The accumulator tile leaves through
+// the dead staging ring as 16-byte pieces of whole rows (restaged_store) where dW is finished
+// here; slabs keep one dword store per accumulator register, which measured faster. IMAGINAIRE_AMD_WGRAD_EPILOGUE=0 restores the dword stores and the
+// slab + finalize path for everything but a plain fp32 single slab; =1 restages everywhere.
 //
 // Reference: the reference's weight gradients come from cuDNN through nn.Conv2d autograd
 // (layers/conv.py:59-91); there is no hand-written conv in the reference.
@@ -64,6 +73,18 @@ struct WgradArgs {
   // unpadded activation and every loader reads the mapped source pixel, so dW is the gradient
   // of the conv of F.pad(x, mode) at padding 0 without the padded copy
   int pmode = 0;
+  // epilogue: 0 = one dword store per accumulator register, 1 = the tile restaged through the
+  // (dead) LDS ring and stored as whole rows, 16 bytes per lane (restaged_store)
+  int epi = 0;
+  // fin != 0 (restaged epilogue, one slab, nb == 1): ``out`` is dW itself, real dims
+  // [oc][KK][oi] in fp32 or bf16 (obf16), rows / columns past oc / oi not stored; ovec: oi % 4
+  // == 0 and the base is aligned for 4-element stores. fin == 2 also applies the spectral-norm
+  // backward from the <G, W> partials sndot[0 .. ndot) (the expression of wgrad_finalize_sn)
+  int fin = 0, oc = 0, oi = 0, obf16 = 0, ovec = 0, ndot = 0;
+  const float* snu = nullptr;
+  const float* snv = nullptr;
+  const float* snsig = nullptr;
+  const float* sndot = nullptr;
 };
 
 // one output's share of <G, W> (outputs in the zero-padded channel tail contribute nothing).
@@ -105,6 +126,100 @@ __device__ __forceinline__ int swz(int row) {
 
 __device__ __forceinline__ bf16x4 tr_read(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t)p);
+}
+
+// ---- restaged epilogue ----------------------------------------------------------------------
+//
+// The MFMA accumulator layout gives a lane 4 rows (n) of one column (ci), so a direct store is
+// one dword per register and a wave instruction covers 4 rows of 64 B. Here the tile goes
+// through the staging ring instead, which is dead once the k-loop has ended (one barrier first:
+// other waves may still be reading fragments), and leaves as whole (n, tap) rows of BC floats,
+// 16 bytes per lane. A unit is the 32 rows x BC columns that the block's four waves hold for
+// one (tap t, fragment row i): rows (wave row wm) * HALF + 16 i + 0..15 of the tile, unit u =
+// t * MI + i. As many units as the ring holds go per pass. Row pitch BC floats, no padding:
+// ds_write_b32 is served in two groups of 32 lanes, each 2 rows of 16 consecutive floats
+// (2-way at most, which costs a dword write nothing), and ds_read_b128's groups of 16 lanes
+// read 256 consecutive bytes of rows that start on a 256-byte boundary (conflict-free).
+//
+// The stores are the same fp32 numbers in the same places as the dword epilogue's. With a.fin
+// (one slab, nothing to sum) the rows are the finished dW instead of a slab: cropped to
+// [oc][KK][oi], cast as wgrad_finalize casts, or with the spectral-norm backward applied as
+// wgrad_finalize_sn applies it — what those kernels compute at S == 1, without the slab.
+__device__ __forceinline__ void finished_store(const WgradArgs& a, const SnCoef& sc, int n,
+                                               int tap, int ci, const f32x4& v) {
+  const int64_t row = ((int64_t)n * a.KK + tap) * a.oi;
+  float x[4] = {v[0], v[1], v[2], v[3]};
+  if (a.fin == 2) {
+    const float cu = sc.cf * a.snu[n];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {  // (columns past oi: clamped load, never stored)
+      const int cc = min(ci + k, a.oi - 1);
+      x[k] = fmaf(x[k], sc.inv, -cu * a.snv[(int64_t)cc * a.KK + tap]);
+    }
+  }
+  __hip_bfloat16* ob = reinterpret_cast<__hip_bfloat16*>(a.out);
+  if (a.ovec) {
+    if (ci < a.oi) {
+      if (a.obf16) store_vec<__hip_bfloat16, 4>(ob + row + ci, x);
+      else store_vec<float, 4>(a.out + row + ci, x);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (ci + k < a.oi) {
+        if (a.obf16) ob[row + ci + k] = __float2bfloat16(x[k]);
+        else a.out[row + ci + k] = x[k];
+      }
+  }
+}
+
+// get(t, i, j, r): accumulator register r of the 16 x 16 fragment (i, j) of tap t. o: the slab
+// of this split (a.fin == 0). n0 / c0: the block's first output / input channel, tap0: its
+// first tap. RING: bytes of the staging ring.
+template <int BC, int HALF, int MI, int NU, int RING, typename Get>
+__device__ __forceinline__ void restaged_store(const WgradArgs& a, char* smem, float* o, int n0,
+                                               int c0, int tap0, Get get) {
+  constexpr int NI = BC / 32;
+  constexpr int C4 = BC / 4;        // 16-byte pieces per row
+  constexpr int UB = 32 * BC * 4;   // bytes per unit
+  constexpr int UP = NU < RING / UB ? NU : RING / UB;  // units per pass
+  static_assert(UP >= 1, "the ring must hold one unit");
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wm = wid >> 1, wn = wid & 1, g = lane >> 4;
+  SnCoef sc{1.f, 0.f};
+  if (a.fin == 2) {
+    __syncthreads();
+    sc = sn_coef<kThreads>(a.sndot, a.ndot, a.snsig, reinterpret_cast<float*>(smem));
+  }
+  float* wr = reinterpret_cast<float*>(smem) + (wm * 16 + g * 4) * BC + wn * (BC / 2) + (lane & 15);
+#pragma unroll
+  for (int u0 = 0; u0 < NU; u0 += UP) {
+    __syncthreads();  // the ring (or the previous pass) has been read by every wave
+#pragma unroll
+    for (int k = 0; k < UP; ++k) {
+      if (u0 + k < NU) {
+        const int t = (u0 + k) / MI, i = (u0 + k) % MI;
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) wr[k * (UB / 4) + r * BC + j * 16] = get(t, i, j, r);
+      }
+    }
+    __syncthreads();
+    const int nu = NU - u0 < UP ? NU - u0 : UP;
+    for (int e = tid; e < nu * 32 * C4; e += kThreads) {
+      const int k = e / (32 * C4), rem = e % (32 * C4);
+      const int rr = rem / C4, c4 = rem % C4;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(smem + k * UB + (rr * BC + c4 * 4) * 4);
+      const int t = (u0 + k) / MI, i = (u0 + k) % MI;
+      const int n = n0 + (rr >> 4) * HALF + i * 16 + (rr & 15);
+      const int ci = c0 + c4 * 4, tap = tap0 + t;
+      if (a.fin == 0)
+        *reinterpret_cast<f32x4*>(o + ((size_t)n * a.KK + tap) * a.Cin + ci) = v;
+      else if (n < a.oc)
+        finished_store(a, sc, n, tap, ci, v);
+    }
+  }
 }
 
 template <int BNO, int BC, bool ROWS, int NST>
@@ -327,6 +442,11 @@ __global__ __launch_bounds__(kThreads, 2) void conv_wgrad_mfma(WgradArgs a) {
           sd += sn_term(a, n0 + wm * (BNO / 2) + i * 16 + g * 4 + r, tap,
                         c0 + wn * (BC / 2) + j * 16 + (lane & 15), acc[i][j][r]);
     sn_dot_store(a, sd);
+  }
+  if (a.epi) {
+    restaged_store<BC, BNO / 2, MI, MI, NST * kStage>(
+        a, smem, o, n0, c0, tap, [&](int, int i, int j, int r) { return acc[i][j][r]; });
+    return;
   }
 #pragma unroll
   for (int i = 0; i < MI; ++i)
@@ -636,6 +756,12 @@ __global__ __launch_bounds__(kThreads, (NT == 5 && BNO == 64) ? 3 : 2) void conv
                           c0 + wn * (BC / 2) + j * 16 + (lane & 15), acc[t][i][j][r]);
     sn_dot_store(a, sd);
   }
+  if (a.epi) {
+    restaged_store<BC, BNO / 2, MI, NT * MI, NST * kStage>(
+        a, smem, o, n0, c0, ky * a.KW,
+        [&](int t, int i, int j, int r) { return acc[t][i][j][r]; });
+    return;
+  }
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int tap = ky * a.KW + t;
@@ -885,6 +1011,12 @@ __global__ __launch_bounds__(kThreads, 1) void conv_wgrad_mfma_w4(WgradArgs a) {
                           c0 + wn * (BC / 2) + j * 16 + (lane & 15), acc[t][i][j][r]);
     sn_dot_store(a, sd);
   }
+  if (a.epi) {
+    restaged_store<BC, 64, 4, NT * 4, NST * kStage>(
+        a, smem, o, n0, c0, ky * a.KW,
+        [&](int t, int i, int j, int r) { return acc[t][i][j][r]; });
+    return;
+  }
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int tap = ky * a.KW + t;
@@ -940,13 +1072,16 @@ bool conv2d_wgrad_v2_eligible(const at::Tensor& dy, const at::Tensor& x, int64_t
 thread_local int g_last_wgrad_kernel = 0;
 int64_t wgrad_last_kernel() { return g_last_wgrad_kernel; }
 
-// variant: 0 = default routing, 1 = never v2, 2 = v2 whenever eligible
-at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
-                             int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
-                             int64_t dw, int64_t out_cout, int64_t out_cin, bool out_bf16,
-                             int64_t nb, int64_t variant,
-                             const c10::optional<std::vector<at::Tensor>>& sn,
-                             const c10::optional<at::Tensor>& dst, int64_t pad_mode) {
+// variant: 0 = default routing, 1 = never v2, 2 = v2 whenever eligible.
+// plan != nullptr: fill it with the decisions (conv2d_wgrad_plan) and return before anything is
+// allocated or launched.
+static at::Tensor wgrad_run(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
+                            int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
+                            int64_t dw, int64_t out_cout, int64_t out_cin, bool out_bf16,
+                            int64_t nb, int64_t variant,
+                            const c10::optional<std::vector<at::Tensor>>& sn,
+                            const c10::optional<at::Tensor>& dst, int64_t pad_mode,
+                            py::dict* plan) {
   IAMD_CHECK(dy.is_cuda() && x.is_cuda(), "conv2d_wgrad_mfma: CUDA tensors expected");
   IAMD_CHECK(dy.scalar_type() == at::kBFloat16 && x.scalar_type() == at::kBFloat16,
              "conv2d_wgrad_mfma: bf16 operands expected");
@@ -1091,12 +1226,41 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
       a.wsn = reinterpret_cast<const __hip_bfloat16*>(shw.data_ptr());
       a.wsn_cout = (int)oc;
       a.wsn_cin = (int)oi;
-      dotp = at::empty({(int64_t)tiles * S}, x.options().dtype(at::kFloat));
-      a.dotp = dotp.data_ptr<float>();
+      if (plan == nullptr) {
+        dotp = at::empty({(int64_t)tiles * S}, x.options().dtype(at::kFloat));
+        a.dotp = dotp.data_ptr<float>();
+      }
     }
   }
   const bool direct = !use_sn && S == 1 && !out_bf16 && oc == Cout && oi == Cin;
-  at::Tensor dW, part;
+  // IMAGINAIRE_AMD_WGRAD_EPILOGUE (read per call): 0 = the dword epilogue and the slab +
+  // wgrad_finalize path everywhere, as before the restaged epilogue; 1 = the restaged epilogue
+  // everywhere (A/B switch, tests); unset or empty = the default below; anything else is an error
+  const char* epi_env = std::getenv("IMAGINAIRE_AMD_WGRAD_EPILOGUE");
+  const bool epi_set = epi_env != nullptr && epi_env[0] != '\0';
+  IAMD_CHECK(!epi_set || ((epi_env[0] == '0' || epi_env[0] == '1') && epi_env[1] == '\0'),
+             "IMAGINAIRE_AMD_WGRAD_EPILOGUE must be 0 or 1, got '", epi_set ? epi_env : "", "'");
+  const bool epi_off = epi_set && epi_env[0] == '0';
+  const bool epi_all = epi_set && epi_env[0] == '1';
+  // One slab of a single weight gradient holds every sum already: the restaged epilogue then
+  // writes the finished dW (crop, cast, or the SN backward from the given <G, W> partials) and
+  // no slab or finalize pass exists. With the 4-element sn, <G, W> comes from this launch's own
+  // epilogue and is complete only after every block: that case keeps the second pass.
+  const bool fin = !epi_off && S == 1 && nb == 1 && !direct && (!use_sn || sn->size() == 5);
+  // Slabs (and the plain fp32 single slab) keep the dword epilogue in every family: switched
+  // within one build the restaged one measured 0-8% slower on them
+  // (profiles/wgrad_epilogue_probe_mi355x.txt)
+  a.epi = !epi_off && (epi_all || fin) ? 1 : 0;
+  const bool rows = Wo % kBP == 0;
+  if (plan != nullptr) {
+    (*plan)["kernel"] = v2 ? 3 : mt ? 2 : rows ? 1 : 0;
+    (*plan)["S"] = S;
+    (*plan)["tiles"] = tiles;
+    (*plan)["finished_in_kernel"] = direct || fin;
+    (*plan)["epilogue"] = a.epi ? "restaged" : "dword";
+    return at::Tensor();
+  }
+  at::Tensor dW, part, snu, snv;
   // dst: the caller's destination for dW (a DDP bucket slice, ops/conv.py): the split-K sum
   // (or the single slab itself) lands there, no copy into the bucket follows
   const bool has_dst = dst.has_value() && dst->defined();
@@ -1114,6 +1278,37 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
                      x.options().dtype(at::kFloat).memory_format(at::MemoryFormat::ChannelsLast));
     }
     a.out = dW.data_ptr<float>();
+  } else if (fin) {
+    const at::ScalarType odt = (out_bf16 && !use_sn) ? at::kBFloat16 : at::kFloat;
+    if (has_dst) {
+      IAMD_CHECK(dst->is_cuda() && dst->scalar_type() == odt && dst->dim() == 4 &&
+                     dst->size(0) == oc && dst->size(1) == oi && dst->size(2) == KH &&
+                     dst->size(3) == KW && dst->is_contiguous(at::MemoryFormat::ChannelsLast),
+                 "conv2d_wgrad_mfma: the destination must be a channels-last [Cout, Cin, KH, KW] "
+                 "tensor of the gradient dtype");
+      dW = *dst;
+    } else {
+      dW = at::empty({oc, oi, KH, KW},
+                     x.options().dtype(odt).memory_format(at::MemoryFormat::ChannelsLast));
+    }
+    if (dW.numel() == 0) return dW;
+    a.out = reinterpret_cast<float*>(dW.data_ptr());
+    a.fin = use_sn ? 2 : 1;
+    a.oc = (int)oc;
+    a.oi = (int)oi;
+    a.obf16 = odt == at::kBFloat16;
+    a.ovec = oi % 4 == 0 && reinterpret_cast<uintptr_t>(dW.data_ptr()) % (a.obf16 ? 8 : 16) == 0;
+    if (use_sn) {
+      snu = (*sn)[1].contiguous();
+      snv = (*sn)[2].contiguous();
+      IAMD_CHECK(snu.is_cuda() && snv.is_cuda() && (*sn)[3].is_cuda(),
+                 "conv2d_wgrad_mfma: SN u / v / sigma must be CUDA tensors");
+      a.snu = snu.data_ptr<float>();
+      a.snv = snv.data_ptr<float>();
+      a.snsig = (*sn)[3].data_ptr<float>();
+      a.sndot = dotp.data_ptr<float>();
+      a.ndot = (int)dotp.numel();
+    }
   } else {
     part = at::empty({(int64_t)S * nb * Cout * KK * Cin}, x.options().dtype(at::kFloat));
     a.out = part.data_ptr<float>();
@@ -1121,7 +1316,6 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
   const int64_t gx = (int64_t)tiles * S;
   IAMD_CHECK(gx < (1ll << 31), "conv2d_wgrad_mfma: grid too large");
   const dim3 grid((unsigned)gx, (unsigned)nb);
-  const bool rows = Wo % kBP == 0;
   g_last_wgrad_kernel = v2 ? 3 : mt ? 2 : rows ? 1 : 0;
   // pipeline depth (IMAGINAIRE_AMD_WGRAD_STAGES = 2 | 3). Default 2: the 3-stage ring with
   // counted vmcnt measured 0.98-1.01x the 2-stage loop on every SPADE-step shape
@@ -1216,7 +1410,7 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
   else if (bc128) launch(I64(), I128());
   else launch(I64(), I64());
   IAMD_LAUNCH_CHECK();
-  if (direct) return dW;
+  if (direct || fin) return dW;
   if (use_sn)
     return wgrad_finalize_sn(part, S, Cout, Cin, oc, oi, KH, KW, dotp, (*sn)[1].contiguous(),
                              (*sn)[2].contiguous(), (*sn)[3], dst);
@@ -1225,6 +1419,30 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
                           out_bf16 ? at::kBFloat16 : at::kFloat, c10::nullopt);
   return wgrad_finalize(part, S, Cout, Cin, oc, oi, KH, KW, out_bf16 ? at::kBFloat16 : at::kFloat,
                         dst);
+}
+
+at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
+                             int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
+                             int64_t dw, int64_t out_cout, int64_t out_cin, bool out_bf16,
+                             int64_t nb, int64_t variant,
+                             const c10::optional<std::vector<at::Tensor>>& sn,
+                             const c10::optional<at::Tensor>& dst, int64_t pad_mode) {
+  return wgrad_run(dy, x, KH, KW, sh, sw, ph, pw, dh, dw, out_cout, out_cin, out_bf16, nb, variant,
+                   sn, dst, pad_mode, nullptr);
+}
+
+// What conv2d_wgrad_mfma would do for the same arguments, launching nothing: kernel (as
+// wgrad_last_kernel), S (split-K slabs), tiles (blocks per slab), finished_in_kernel (the k11
+// kernel writes dW itself, no wgrad_finalize pass), epilogue ("restaged" | "dword").
+py::dict conv2d_wgrad_plan(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
+                           int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
+                           int64_t out_cout, int64_t out_cin, bool out_bf16, int64_t nb,
+                           int64_t variant, const c10::optional<std::vector<at::Tensor>>& sn,
+                           const c10::optional<at::Tensor>& dst, int64_t pad_mode) {
+  py::dict d;
+  wgrad_run(dy, x, KH, KW, sh, sw, ph, pw, dh, dw, out_cout, out_cin, out_bf16, nb, variant, sn,
+            dst, pad_mode, &d);
+  return d;
 }
 
 }  // namespace iamd
