@@ -89,6 +89,15 @@ bool stream_capturing();
 void mt_scale(const std::vector<at::Tensor>& xs, const at::Tensor& s);
 at::Tensor mt_sqnorm(const std::vector<at::Tensor>& xs);
 uint64_t mt_table_key(const std::vector<std::vector<at::Tensor>>& lists);
+void mt_fromage(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                const std::vector<at::Tensor>& shadows, double lr,
+                const c10::optional<at::Tensor>& hyper);
+void mt_madam_init(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& states,
+                   double scale);
+void mt_madam(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+              const std::vector<at::Tensor>& exp_avg_sqs, const std::vector<at::Tensor>& shadows,
+              const std::vector<at::Tensor>& states, double lr,
+              const c10::optional<double>& g_bound, const c10::optional<at::Tensor>& hyper);
 // correlation.hip (k6 correlation, k8 channelnorm)
 std::vector<at::Tensor> attention_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                       double scale);
@@ -348,6 +357,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mt_table_key", &iamd::mt_table_key,
         "cache key of the device table of up to 5 parallel tensor lists (launches nothing)",
         py::arg("lists"));
+  m.def("mt_fromage", &iamd::mt_fromage, "multi-tensor Fromage step", py::arg("params"),
+        py::arg("grads"), py::arg("shadows"), py::arg("lr"), py::arg("hyper") = py::none());
+  m.def("mt_madam_init", &iamd::mt_madam_init,
+        "Madam clamp bound: states[i][1] = scale * sqrt(mean(params[i]^2))", py::arg("params"),
+        py::arg("states"), py::arg("scale"));
+  m.def("mt_madam", &iamd::mt_madam, "multi-tensor Madam step", py::arg("params"),
+        py::arg("grads"), py::arg("exp_avg_sqs"), py::arg("shadows"), py::arg("state"),
+        py::arg("lr"), py::arg("g_bound") = py::none(), py::arg("hyper") = py::none());
   m.def("mt_l1_loss", &iamd::mt_l1_loss, "multi-tensor weighted L1 loss (k13)");
   m.def("mt_l1_loss_backward", &iamd::mt_l1_loss_backward, "k13 backward");
   m.def("mt_gan_loss", &iamd::mt_gan_loss, "multi-tensor GAN loss over D outputs (k13b)");

@@ -15,6 +15,9 @@
 //                 absorbs spectral norm into the averaged model)
 //   mt_scale    : x *= s (gradient clipping / unscale)
 //   mt_sqnorm   : Σ x² per list (gradient-norm for clipping)
+//   mt_fromage  : Fromage (optimizers/fromage.py): per-tensor |p|, |g| in a fixed-order reduce,
+//                 then one update pass; the zero-norm branch is taken on the device
+//   mt_madam    : Madam (optimizers/madam.py): per-parameter {step, max} live on the device
 #include "common.h"
 
 #include <cstdlib>
@@ -520,6 +523,261 @@ sqnorm_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ bloc
   }
 }
 
+// ---- Fromage / Madam (reference optimizers/fromage.py, optimizers/madam.py) --------------------
+// Both follow adam_kernel's chunking: one kChunk slice per workgroup, a 16-byte vector body with
+// U groups of loads in flight per lane, a scalar tail for the last 1..3 elements and a scalar
+// fallback when an operand is off the vector alignment. Everything a step decides (Fromage's
+// zero-norm branch, Madam's bias correction and clamp bound) is decided on the device, so the
+// step records into a hipGraph as it is.
+
+// Fromage pass 1: part[b] = {Σ p², Σ g²} over workgroup b's chunk. p0 = p (fp32), p1 = g.
+template <typename G>
+__global__ void __launch_bounds__(kThreads)
+fromage_norm_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks,
+                    float* __restrict__ part) {
+  __shared__ float sh[2][kThreads / 64];
+  const int b = blockIdx.x;
+  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
+  const TensorEntry e = ents[t];
+  const float* __restrict__ p = reinterpret_cast<const float*>(e.p[0]);
+  const G* __restrict__ g = reinterpret_cast<const G*>(e.p[1]);
+  const int64_t start = (int64_t)chunk * kChunk;
+  const int64_t end = min(e.numel, start + (int64_t)kChunk);
+  float ap = 0.f, ag = 0.f;
+  const bool vec_ok = ((uintptr_t)p % 16 == 0) && ((uintptr_t)g % (4 * sizeof(G)) == 0);
+  if (vec_ok) {
+    constexpr int U = 4;
+    const int64_t vend = start + ((end - start) & ~(int64_t)3);
+    for (int64_t base = start + threadIdx.x * 4; base < vend; base += kThreads * 4 * U) {
+      float pv[U][4], gv[U][4];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (int64_t)u * kThreads * 4;
+        if (i < vend) {
+          ld4<true>(p + i, pv[u]);
+          load_vec<G, 4>(g + i, gv[u]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) pv[u][k] = gv[u][k] = 0.f;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          ap = fmaf(pv[u][k], pv[u][k], ap);
+          ag = fmaf(gv[u][k], gv[u][k], ag);
+        }
+    }
+    for (int64_t i = vend + threadIdx.x; i < end; i += kThreads) {
+      const float pv = p[i], gv = to_f<G>(g[i]);
+      ap = fmaf(pv, pv, ap);
+      ag = fmaf(gv, gv, ag);
+    }
+  } else {
+    for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
+      const float pv = p[i], gv = to_f<G>(g[i]);
+      ap = fmaf(pv, pv, ap);
+      ag = fmaf(gv, gv, ag);
+    }
+  }
+  ap = wave_sum(ap);
+  ag = wave_sum(ag);
+  if ((threadIdx.x & 63) == 0) {
+    sh[0][threadIdx.x >> 6] = ap;
+    sh[1][threadIdx.x >> 6] = ag;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    float s = 0.f;
+    for (int k = 0; k < kThreads / 64; ++k) s += sh[threadIdx.x][k];
+    part[2 * b + threadIdx.x] = s;
+  }
+}
+
+// Two-output sibling of reduce_block_partials: out[t] = {Σ part[b][0], Σ part[b][1]} over the
+// workgroups of tensor t, one workgroup per tensor, in one fixed order.
+__global__ void __launch_bounds__(kThreads)
+reduce_block_partials2(const float* __restrict__ part, const int* __restrict__ blocks,
+                       int nblocks, float* __restrict__ out) {
+  __shared__ float sh[2][kThreads / 64];
+  const int t = blockIdx.x;
+  float a0 = 0.f, a1 = 0.f;
+  for (int b = threadIdx.x; b < nblocks; b += kThreads)
+    if (blocks[2 * b] == t) {
+      a0 += part[2 * b];
+      a1 += part[2 * b + 1];
+    }
+  a0 = wave_sum(a0);
+  a1 = wave_sum(a1);
+  if ((threadIdx.x & 63) == 0) {
+    sh[0][threadIdx.x >> 6] = a0;
+    sh[1][threadIdx.x >> 6] = a1;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    float s = 0.f;
+    for (int k = 0; k < kThreads / 64; ++k) s += sh[threadIdx.x][k];
+    out[2 * t + threadIdx.x] = s;
+  }
+}
+
+// Fromage pass 2: p = (p - lr * ratio * g) / sqrt(1 + lr²), ratio = |p| / |g| of the whole
+// tensor when both norms are positive, else 1 (taken per tensor, here). p2 = bf16 shadow.
+template <typename G>
+__global__ void __launch_bounds__(kThreads)
+fromage_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks,
+               const float* __restrict__ norms, float lr, const float* __restrict__ hyper) {
+  const int b = blockIdx.x;
+  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
+  const TensorEntry e = ents[t];
+  float* __restrict__ p = reinterpret_cast<float*>(e.p[0]);
+  const G* __restrict__ g = reinterpret_cast<const G*>(e.p[1]);
+  __hip_bfloat16* __restrict__ shadow = reinterpret_cast<__hip_bfloat16*>(e.p[2]);
+  const int64_t start = (int64_t)chunk * kChunk;
+  const int64_t end = min(e.numel, start + (int64_t)kChunk);
+  if (hyper) lr = hyper[0];
+  const float pn = sqrtf(norms[2 * t]), gn = sqrtf(norms[2 * t + 1]);
+  const float na = -lr * ((pn > 0.f && gn > 0.f) ? pn / gn : 1.f);
+  const float c = 1.f / sqrtf(fmaf(lr, lr, 1.f));
+  const bool vec_ok = ((uintptr_t)p % 16 == 0) && ((uintptr_t)g % (4 * sizeof(G)) == 0) &&
+                      ((uintptr_t)shadow % 8 == 0);
+  if (vec_ok) {
+    constexpr int U = 4;
+    const int64_t vend = start + ((end - start) & ~(int64_t)3);
+    for (int64_t base = start + threadIdx.x * 4; base < vend; base += kThreads * 4 * U) {
+      float pv[U][4], gv[U][4];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (int64_t)u * kThreads * 4;
+        if (i < vend) {
+          ld4<true>(p + i, pv[u]);
+          load_vec<G, 4>(g + i, gv[u]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (int64_t)u * kThreads * 4;
+        if (i >= vend) continue;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pv[u][k] = fmaf(na, gv[u][k], pv[u][k]) * c;
+        st4<true>(p + i, pv[u]);
+        if (shadow) store_vec<__hip_bfloat16, 4>(shadow + i, pv[u]);
+      }
+    }
+    for (int64_t i = vend + threadIdx.x; i < end; i += kThreads) {
+      const float pv = fmaf(na, to_f<G>(g[i]), p[i]) * c;
+      p[i] = pv;
+      if (shadow) shadow[i] = __float2bfloat16(pv);
+    }
+  } else {
+    for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
+      const float pv = fmaf(na, to_f<G>(g[i]), p[i]) * c;
+      p[i] = pv;
+      if (shadow) shadow[i] = __float2bfloat16(pv);
+    }
+  }
+}
+
+// Madam's per-parameter device state is {step, max} (fp32, table slot p4).
+// state[1] = scale * sqrt(mean(p²)) from the per-tensor Σ p² (p0 = p, p1 = state).
+__global__ void __launch_bounds__(kThreads)
+madam_max_kernel(const TensorEntry* __restrict__ ents, int ntensors,
+                 const float* __restrict__ sums, float scale) {
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  if (t >= ntensors) return;
+  float* __restrict__ st = reinterpret_cast<float*>(ents[t].p[1]);
+  const int64_t n = ents[t].numel;
+  if (st) st[1] = n > 0 ? scale * sqrtf(sums[t] / (float)n) : 0.f;
+}
+
+// Prologue of every Madam step: each listed parameter's own step count moves on by one.
+__global__ void __launch_bounds__(kThreads)
+madam_step_kernel(const TensorEntry* __restrict__ ents, int ntensors) {
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  if (t >= ntensors) return;
+  float* __restrict__ st = reinterpret_cast<float*>(ents[t].p[4]);
+  if (st) st[0] += 1.f;
+}
+
+// One Madam update of an element. sbc = sqrt(bias correction): g / sqrt(v / bc) is evaluated as
+// g * sqrt(bc) / sqrt(v), one square root and one division per element.
+__device__ __forceinline__ void madam_update(float& p, float g, float& v, float sbc, float nlr,
+                                             float bound, float mx) {
+  v = fmaf(0.999f, v, 0.001f * (g * g));
+  float gn = g * sbc / sqrtf(v);
+  gn = gn != gn ? 0.f : gn;  // 0 / 0: a gradient that has been zero since the first step
+  if (bound >= 0.f) gn = fminf(fmaxf(gn, -bound), bound);
+  const float sg = p > 0.f ? 1.f : (p < 0.f ? -1.f : 0.f);
+  p *= expf(nlr * gn * sg);
+  p = fminf(fmaxf(p, -mx), mx);
+}
+
+// p0 = p (fp32), p1 = g, p2 = exp_avg_sq, p3 = bf16 shadow, p4 = state {step, max}.
+// bound < 0: no gradient clamp.
+template <typename G>
+__global__ void __launch_bounds__(kThreads)
+madam_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks, float lr,
+             float bound, const float* __restrict__ hyper) {
+  const int b = blockIdx.x;
+  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
+  const TensorEntry e = ents[t];
+  float* __restrict__ p = reinterpret_cast<float*>(e.p[0]);
+  const G* __restrict__ g = reinterpret_cast<const G*>(e.p[1]);
+  float* __restrict__ v = reinterpret_cast<float*>(e.p[2]);
+  __hip_bfloat16* __restrict__ shadow = reinterpret_cast<__hip_bfloat16*>(e.p[3]);
+  const float* __restrict__ st = reinterpret_cast<const float*>(e.p[4]);
+  const int64_t start = (int64_t)chunk * kChunk;
+  const int64_t end = min(e.numel, start + (int64_t)kChunk);
+  if (hyper) lr = hyper[0];
+  const float nlr = -lr;
+  // once per workgroup: bc = 1 - 0.999^step = -expm1(step * ln 0.999) (the form that keeps its
+  // precision at small step counts, where 0.999^step is close to 1)
+  const float sbc = sqrtf(-expm1f(st[0] * -1.0005003335835335e-3f));
+  const float mx = st[1];
+  const bool vec_ok = (((uintptr_t)p | (uintptr_t)v) % 16 == 0) &&
+                      ((uintptr_t)g % (4 * sizeof(G)) == 0) && ((uintptr_t)shadow % 8 == 0);
+  if (vec_ok) {
+    constexpr int U = 4;
+    const int64_t vend = start + ((end - start) & ~(int64_t)3);
+    for (int64_t base = start + threadIdx.x * 4; base < vend; base += kThreads * 4 * U) {
+      float pv[U][4], gv[U][4], vv[U][4];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (int64_t)u * kThreads * 4;
+        if (i < vend) {
+          ld4<true>(p + i, pv[u]);
+          load_vec<G, 4>(g + i, gv[u]);
+          ld4<true>(v + i, vv[u]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (int64_t)u * kThreads * 4;
+        if (i >= vend) continue;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) madam_update(pv[u][k], gv[u][k], vv[u][k], sbc, nlr, bound, mx);
+        st4<true>(v + i, vv[u]);
+        st4<true>(p + i, pv[u]);
+        if (shadow) store_vec<__hip_bfloat16, 4>(shadow + i, pv[u]);
+      }
+    }
+    for (int64_t i = vend + threadIdx.x; i < end; i += kThreads) {
+      float pv = p[i], vv = v[i];
+      madam_update(pv, to_f<G>(g[i]), vv, sbc, nlr, bound, mx);
+      v[i] = vv; p[i] = pv;
+      if (shadow) shadow[i] = __float2bfloat16(pv);
+    }
+  } else {
+    for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
+      float pv = p[i], vv = v[i];
+      madam_update(pv, to_f<G>(g[i]), vv, sbc, nlr, bound, mx);
+      v[i] = vv; p[i] = pv;
+      if (shadow) shadow[i] = __float2bfloat16(pv);
+    }
+  }
+}
+
 void check_same_dtype(const std::vector<at::Tensor>& l, at::ScalarType st, const char* what) {
   for (auto& t : l) {
     IAMD_CHECK(t.scalar_type() == st, what, ": dtype mismatch");
@@ -712,6 +970,136 @@ at::Tensor mt_sqnorm(const std::vector<at::Tensor>& xs) {
                      out.data_ptr<float>());
   IAMD_LAUNCH_CHECK();
   return out;
+}
+
+namespace {
+
+// The device learning rate of mt_fromage / mt_madam: hyper[0] (a replayed graph sees a changed
+// value); null = use the host argument.
+const float* lr_hyper(const c10::optional<at::Tensor>& hyper, const char* what) {
+  if (!hyper.has_value() || !hyper->defined()) return nullptr;
+  IAMD_CHECK(hyper->is_cuda() && hyper->scalar_type() == at::kFloat && hyper->numel() >= 1 &&
+                 hyper->is_contiguous(),
+             what, ": hyper must be a contiguous fp32 device tensor [lr, ...]");
+  return hyper->data_ptr<float>();
+}
+
+// Optional bf16 shadows, one per parameter (an empty tensor = none for that parameter); an empty
+// list = none at all, returned as a list of empty tensors so the table slots stay put.
+std::vector<at::Tensor> shadow_list(const std::vector<at::Tensor>& shadows,
+                                    const std::vector<at::Tensor>& params, const char* what) {
+  if (shadows.empty())
+    return std::vector<at::Tensor>(params.size(),
+                                   at::empty({0}, params[0].options().dtype(at::kBFloat16)));
+  IAMD_CHECK(shadows.size() == params.size(), what, ": shadow list size");
+  for (size_t i = 0; i < shadows.size(); ++i) {
+    if (shadows[i].numel() == 0) continue;
+    IAMD_CHECK(shadows[i].scalar_type() == at::kBFloat16 && shadows[i].is_cuda() &&
+                   shadows[i].sizes() == params[i].sizes() &&
+                   shadows[i].strides() == params[i].strides(),
+               what, ": a shadow must be a bf16 tensor laid out like its parameter");
+  }
+  return shadows;
+}
+
+void check_madam_states(const std::vector<at::Tensor>& states, size_t n, const char* what) {
+  IAMD_CHECK(states.size() == n, what, ": state list size");
+  for (auto& s : states)
+    IAMD_CHECK(s.is_cuda() && s.scalar_type() == at::kFloat && s.dim() == 1 && s.numel() == 2 &&
+                   s.is_contiguous(),
+               what, ": a state must be a contiguous fp32 device tensor [step, max]");
+}
+
+}  // namespace
+
+void mt_fromage(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                const std::vector<at::Tensor>& shadows, double lr,
+                const c10::optional<at::Tensor>& hyper) {
+  if (params.empty()) return;
+  const float* hp = lr_hyper(hyper, "mt_fromage");
+  IAMD_CHECK(params.size() == grads.size(), "mt_fromage: list sizes differ");
+  check_same_dtype(params, at::kFloat, "mt_fromage params");
+  const auto gdt = grads[0].scalar_type();
+  IAMD_CHECK(gdt == at::kFloat || gdt == at::kBFloat16, "mt_fromage: grads must be fp32 or bf16");
+  check_same_dtype(grads, gdt, "mt_fromage grads");
+  Table& tb = get_table({params, grads, shadow_list(shadows, params, "mt_fromage")},
+                        params[0].device());
+  if (tb.nblocks == 0) return;
+  const int T = (int)params.size();
+  auto ents = reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr());
+  auto blks = tb.blocks.data_ptr<int>();
+  // (both fully written by the kernels below: no memset node in a captured step)
+  auto part = at::empty({(int64_t)tb.nblocks, 2}, params[0].options());
+  auto norms = at::empty({(int64_t)T, 2}, params[0].options());
+#define IAMD_FROMAGE_LAUNCH(G)                                                                  \
+  do {                                                                                          \
+    hipLaunchKernelGGL((fromage_norm_kernel<G>), dim3(tb.nblocks), dim3(kThreads), 0, stream(), \
+                       ents, blks, part.data_ptr<float>());                                     \
+    hipLaunchKernelGGL(reduce_block_partials2, dim3(T), dim3(kThreads), 0, stream(),            \
+                       part.data_ptr<float>(), blks, tb.nblocks, norms.data_ptr<float>());      \
+    hipLaunchKernelGGL((fromage_kernel<G>), dim3(tb.nblocks), dim3(kThreads), 0, stream(), ents, \
+                       blks, norms.data_ptr<float>(), (float)lr, hp);                           \
+  } while (0)
+  if (gdt == at::kFloat) IAMD_FROMAGE_LAUNCH(float);
+  else IAMD_FROMAGE_LAUNCH(__hip_bfloat16);
+#undef IAMD_FROMAGE_LAUNCH
+  IAMD_LAUNCH_CHECK();
+}
+
+// state[i][1] = scale * sqrt(mean(params[i]²)): Madam's clamp bound, taken from a parameter
+// before its first update, without a host read.
+void mt_madam_init(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& states,
+                   double scale) {
+  if (params.empty()) return;
+  check_same_dtype(params, at::kFloat, "mt_madam_init params");
+  check_madam_states(states, params.size(), "mt_madam_init");
+  Table& tb = get_table({params, states}, params[0].device());
+  const int T = (int)params.size();
+  auto ents = reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr());
+  auto sums = at::empty({(int64_t)T}, params[0].options());
+  auto part = at::empty({(int64_t)std::max(tb.nblocks, 1)}, params[0].options());
+  if (tb.nblocks)
+    hipLaunchKernelGGL((sqnorm_kernel<float>), dim3(tb.nblocks), dim3(kThreads), 0, stream(), ents,
+                       tb.blocks.data_ptr<int>(), part.data_ptr<float>());
+  hipLaunchKernelGGL(reduce_block_partials, dim3(T), dim3(kThreads), 0, stream(),
+                     part.data_ptr<float>(), tb.blocks.data_ptr<int>(), tb.nblocks, false,
+                     sums.data_ptr<float>());
+  hipLaunchKernelGGL(madam_max_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                     stream(), ents, T, sums.data_ptr<float>(), (float)scale);
+  IAMD_LAUNCH_CHECK();
+}
+
+void mt_madam(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+              const std::vector<at::Tensor>& exp_avg_sqs, const std::vector<at::Tensor>& shadows,
+              const std::vector<at::Tensor>& states, double lr,
+              const c10::optional<double>& g_bound, const c10::optional<at::Tensor>& hyper) {
+  if (params.empty()) return;
+  const float* hp = lr_hyper(hyper, "mt_madam");
+  IAMD_CHECK(params.size() == grads.size() && params.size() == exp_avg_sqs.size(),
+             "mt_madam: list sizes differ");
+  check_same_dtype(params, at::kFloat, "mt_madam params");
+  check_same_dtype(exp_avg_sqs, at::kFloat, "mt_madam exp_avg_sq");
+  const auto gdt = grads[0].scalar_type();
+  IAMD_CHECK(gdt == at::kFloat || gdt == at::kBFloat16, "mt_madam: grads must be fp32 or bf16");
+  check_same_dtype(grads, gdt, "mt_madam grads");
+  check_madam_states(states, params.size(), "mt_madam");
+  IAMD_CHECK(!g_bound.has_value() || *g_bound >= 0.0, "mt_madam: g_bound must be >= 0 or None");
+  Table& tb = get_table({params, grads, exp_avg_sqs, shadow_list(shadows, params, "mt_madam"),
+                         states}, params[0].device());
+  const int T = (int)params.size();
+  auto ents = reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr());
+  hipLaunchKernelGGL(madam_step_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                     stream(), ents, T);
+  const float bound = g_bound.has_value() ? (float)*g_bound : -1.f;
+  if (tb.nblocks) {
+    if (gdt == at::kFloat)
+      hipLaunchKernelGGL((madam_kernel<float>), dim3(tb.nblocks), dim3(kThreads), 0, stream(),
+                         ents, tb.blocks.data_ptr<int>(), (float)lr, bound, hp);
+    else
+      hipLaunchKernelGGL((madam_kernel<__hip_bfloat16>), dim3(tb.nblocks), dim3(kThreads), 0,
+                         stream(), ents, tb.blocks.data_ptr<int>(), (float)lr, bound, hp);
+  }
+  IAMD_LAUNCH_CHECK();
 }
 
 }  // namespace iamd

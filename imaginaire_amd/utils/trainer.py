@@ -2,8 +2,8 @@
 
 Same flow as the reference: identical-seed weight init on every rank, then a
 rank-offset seed; G/D built from ``cfg.gen.type`` / ``cfg.dis.type``; optimizers
-from ``cfg.{gen,dis}_opt`` (adam → the fused multi-tensor HIP Adam when
-``fused_opt``); ``ModelAverage`` wrapping; data-parallel wrapping.
+from ``cfg.{gen,dis}_opt`` (adam / fromage / madam → their fused multi-tensor
+HIP versions when ``fused_opt``); ``ModelAverage`` wrapping; data-parallel wrapping.
 
 MI355X mapping of the reference knobs:
   * ``trainer.amp`` O1/O2 → bf16 autocast (no loss scaler), O0 → fp32;
@@ -23,7 +23,7 @@ import torch.nn as nn
 from imaginaire_amd.layers.spectral_norm import install_batched_spectral_norm
 from torch.optim import SGD, Adam, RMSprop, lr_scheduler
 
-from imaginaire_amd.optimizers import Fromage, Madam, FusedAdam
+from imaginaire_amd.optimizers import Fromage, Madam, FusedAdam, FusedFromage, FusedMadam
 from imaginaire_amd.parallel import DistributedDataParallel, WrappedModel
 from imaginaire_amd.parallel.groups import assign_syncbn_group
 from imaginaire_amd.registry import import_module
@@ -180,10 +180,12 @@ def get_optimizer_for_params(cfg_opt, params):
             return FusedAdam(params, lr=cfg_opt.lr, eps=eps, betas=betas)
         return Adam(params, lr=cfg_opt.lr, eps=eps, betas=betas)
     if cfg_opt.type == 'madam':
-        return Madam(params, lr=cfg_opt.lr, scale=getattr(cfg_opt, 'scale', 3.0),
-                     g_bound=getattr(cfg_opt, 'g_bound', None))
+        cls = FusedMadam if fused_opt else Madam
+        return cls(params, lr=cfg_opt.lr, scale=getattr(cfg_opt, 'scale', 3.0),
+                   g_bound=getattr(cfg_opt, 'g_bound', None))
     if cfg_opt.type == 'fromage':
-        return Fromage(params, lr=cfg_opt.lr)
+        cls = FusedFromage if fused_opt else Fromage
+        return cls(params, lr=cfg_opt.lr)
     if cfg_opt.type == 'rmsprop':
         return RMSprop(params, lr=cfg_opt.lr, eps=eps,
                        weight_decay=getattr(cfg_opt, 'weight_decay', 0))
