@@ -115,6 +115,12 @@ py::dict correlation_plan(const at::Tensor& input1, int64_t pad, int64_t ks, int
 at::Tensor channelnorm_forward(const at::Tensor& x);
 at::Tensor channelnorm_backward(const at::Tensor& x, const at::Tensor& out,
                                 const at::Tensor& grad_out);
+// roi_crop.hip (k17 part boxes, box crop + resize)
+at::Tensor part_bbox(const at::Tensor& label, std::vector<int64_t> channels, int64_t rule,
+                     bool eq, double ref, int64_t crop_smaller);
+at::Tensor roi_crop_fwd(const at::Tensor& image, const at::Tensor& boxes, int64_t oh,
+                        int64_t ow);
+at::Tensor roi_crop_bwd(const at::Tensor& dy, const at::Tensor& boxes, const at::Tensor& like);
 // flow_warp.hip (k9 warp, k7 resample2d)
 at::Tensor flow_warp_fwd(const at::Tensor& img, const at::Tensor& flow);
 std::vector<at::Tensor> flow_warp_bwd(const at::Tensor& img, const at::Tensor& flow,
@@ -374,6 +380,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resize_bilinear_bwd", &iamd::resize_bilinear_bwd, "k12 backward (gather)");
   m.def("resize_nearest_fwd", &iamd::resize_nearest_fwd, "NHWC nearest resize (k12)");
   m.def("resize_nearest_bwd", &iamd::resize_nearest_bwd, "k12 nearest backward (gather)");
+  m.def("part_bbox", &iamd::part_bbox,
+        "per-sample part boxes (ys, ye, xs, xe, valid), box rule on the device (k17)");
+  m.def("roi_crop_fwd", &iamd::roi_crop_fwd,
+        "crop to device boxes + bilinear resize of the last 3 channels (k17)");
+  m.def("roi_crop_bwd", &iamd::roi_crop_bwd, "k17 backward (gather over the whole image)");
   m.def("flow_warp_fwd", &iamd::flow_warp_fwd, "bilinear flow warp, border (k9)");
   m.def("flow_warp_bwd", &iamd::flow_warp_bwd, "k9 backward", py::arg("img"), py::arg("flow"),
         py::arg("dout"), py::arg("need_dimg") = true);

@@ -77,10 +77,12 @@ class Discriminator(nn.Module):
                 mod, fn = self.add_dis_cfg[name].crop_func.split('::')
                 crop_func = getattr(importlib.import_module(
                     mod.replace('imaginaire.', 'imaginaire_amd.', 1)), fn)
-                real_crop = crop_func(self.data_cfg, real_image, label)
-                fake_crop = crop_func(self.data_cfg, fake_image, label)
+                # one call for all images: the label is scanned for its boxes once
+                images = [real_image, fake_image] + ([ref_image] if self.use_few_shot else [])
+                crops = crop_func(self.data_cfg, images, label)
+                real_crop, fake_crop = crops[0], crops[1]
                 if self.use_few_shot:
-                    ref_crop = crop_func(self.data_cfg, ref_image, label)
+                    ref_crop = crops[2]
                     if ref_crop is not None:
                         real_crop = torch.cat([real_crop, ref_crop], dim=1)
                         fake_crop = torch.cat([fake_crop, ref_crop], dim=1)

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from imaginaire_amd.ops.flow_warp import flow_warp
+from imaginaire_amd.ops.roi_crop import part_bbox, roi_crop_resize
 
 
 def resample(image, flow):
@@ -115,10 +116,19 @@ _PART_GROUPS = [[0], [1, 2], [3, 4], [5, 6], [7, 9, 8, 10], [11, 13, 12, 14],
                 [15, 17, 16, 18], [19, 21, 20, 22], [23, 24]]
 
 
+def _assert_part_range(part):
+    """Part ids lie in [0, 25). A host read of device data: skipped while the stream is being
+    captured into a hipGraph (``pre_process_densepose`` makes the same check on the batch
+    before the step begins)."""
+    if part.is_cuda and torch.cuda.is_current_stream_capturing():
+        return
+    assert (part >= 0).all() and (part < 25).all()
+
+
 def _part_index(densepose_map):
     """DensePose part channel in [-1, 1] -> part id in [0, 24] (rounded)."""
     part = (densepose_map / 2 + 0.5) * 24
-    assert (part >= 0).all() and (part < 25).all()
+    _assert_part_range(part)
     return torch.round(part)
 
 
@@ -145,7 +155,7 @@ def get_part_mask(densepose_map):
         bo, t, h, w = densepose_map.shape
         densepose_map = densepose_map.reshape(-1, h, w)
     part = (densepose_map / 2 + 0.5) * 24
-    assert (part >= 0).all() and (part < 25).all()
+    _assert_part_range(part)
     masks = []
     for group in _PART_GROUPS:
         m = torch.zeros_like(part, dtype=torch.bool)
@@ -161,7 +171,7 @@ def get_part_mask(densepose_map):
 def get_face_mask(densepose_map):
     """Face (parts 23, 24) mask (fs_vid2vid.py:496-519)."""
     part = (densepose_map / 2 + 0.5) * 24
-    assert (part >= 0).all() and (part < 25).all()
+    _assert_part_range(part)
     m = ((part > 22.9) & (part < 23.1)) | ((part > 23.9) & (part < 24.1))
     return m.float()
 
@@ -403,10 +413,11 @@ def get_face_bbox_for_output(data_cfg, pose, crop_smaller=0):
     return [ys, ye, xs, xe]
 
 
-def crop_face_from_output(data_cfg, image, input_label, crop_smaller=0):
-    """Crop + resize the face of every sample (fs_vid2vid.py:631-658)."""
+def _crop_face_per_sample(data_cfg, image, input_label, crop_smaller=0):
+    """The reference's per-sample crop: host-side boxes (CPU tensors; the oracle of the device
+    path in tests/test_roi_crop_gpu.py)."""
     if isinstance(image, list):
-        return [crop_face_from_output(data_cfg, im, input_label, crop_smaller) for im in image]
+        return [_crop_face_per_sample(data_cfg, im, input_label, crop_smaller) for im in image]
     face_size = image.shape[-2] // 32 * 8
     crops = []
     for i in range(input_label.size(0)):
@@ -416,6 +427,46 @@ def crop_face_from_output(data_cfg, image, input_label, crop_smaller=0):
                                    size=(face_size, face_size), mode='bilinear',
                                    align_corners=True))
     return torch.cat(crops)
+
+
+def _on_device(image, input_label, min_side):
+    """The crops of GPU batches run on ops/roi_crop.py (boxes never leave the device)."""
+    kernel_dtypes = (torch.float32, torch.bfloat16)
+
+    def ok(t):
+        return torch.is_tensor(t) and t.is_cuda and t.dim() == 4 and t.dtype in kernel_dtypes \
+            and t.shape[-2:] == input_label.shape[-2:]
+    images = image if isinstance(image, list) else [image]
+    return len(images) > 0 and ok(input_label) and all(ok(im) for im in images) and \
+        input_label.shape[-2] >= min_side
+
+
+def _face_bbox_on_device(data_cfg, input_label, crop_smaller):
+    if 'pose_maps-densepose' in data_cfg.input_labels:
+        return part_bbox(input_label, 2, rule='face_densepose', threshold=0.9,
+                         crop_smaller=crop_smaller)
+    num_ch = 0
+    for input_type in data_cfg.input_types:
+        if 'poses-openpose' in input_type:
+            num_ch = input_type['poses-openpose'].num_channels
+    if num_ch <= 3:
+        raise ValueError('Not implemented yet.')
+    return part_bbox(input_label, -1, rule='face_openpose', threshold=0,
+                     crop_smaller=crop_smaller)
+
+
+def crop_face_from_output(data_cfg, image, input_label, crop_smaller=0):
+    """Crop + resize the face of every sample (fs_vid2vid.py:631-658). ``image`` may be a list
+    of images that share ``input_label``: the boxes are then found once. On GPU tensors: one
+    ``part_bbox`` and one ``roi_crop_resize`` per image for the whole batch, no host read."""
+    if not _on_device(image, input_label, 32):
+        return _crop_face_per_sample(data_cfg, image, input_label, crop_smaller)
+    boxes = _face_bbox_on_device(data_cfg, input_label, crop_smaller)
+
+    def crop(im):
+        face_size = im.shape[-2] // 32 * 8
+        return roi_crop_resize(im, boxes, (face_size, face_size))
+    return [crop(im) for im in image] if isinstance(image, list) else crop(image)
 
 
 def get_hand_bbox_for_output(data_cfg, pose):
@@ -441,11 +492,34 @@ def get_hand_bbox_for_output(data_cfg, pose):
     return coords
 
 
-def crop_hand_from_output(data_cfg, image, input_label):
+def _crop_hand_per_sample(data_cfg, image, input_label):
+    """The reference's per-sample hand crop (host-side boxes)."""
     if isinstance(image, list):
-        return [crop_hand_from_output(data_cfg, im, input_label) for im in image]
+        return [_crop_hand_per_sample(data_cfg, im, input_label) for im in image]
     crops = []
     for i in range(input_label.size(0)):
         for ys, ye, xs, xe in get_hand_bbox_for_output(data_cfg, input_label[i:i + 1]):
             crops.append(image[i:i + 1, -3:, ys:ye, xs:xe])
     return torch.cat(crops) if crops else None
+
+
+def crop_hand_from_output(data_cfg, image, input_label):
+    """Crops of the hands present in each sample, sample-major, or None without any
+    (fs_vid2vid.py:717-740). ``image`` may be a list of images that share ``input_label``. On
+    GPU tensors: one ``part_bbox`` over both hand channels, one box-size ``roi_crop_resize``
+    (a plain copy) per image, and ONE read-back of the [B, 2] valid flags to drop absent
+    hands."""
+    if not _on_device(image, input_label, 64):
+        return _crop_hand_per_sample(data_cfg, image, input_label)
+    if input_label.shape[1] <= 6:
+        raise ValueError('Not implemented yet.')
+    boxes = part_bbox(input_label, (-3, -2), rule='hand', equals=1)
+    keep = boxes[..., 4].reshape(-1).bool().cpu()  # the one host read of the call
+    if not bool(keep.any()):
+        return [None] * len(image) if isinstance(image, list) else None
+    keep = keep.nonzero().reshape(-1).to(boxes.device)
+    size = input_label.shape[-2] // 64 * 8
+
+    def crop(im):
+        return roi_crop_resize(im, boxes, (size, size)).index_select(0, keep)
+    return [crop(im) for im in image] if isinstance(image, list) else crop(image)
