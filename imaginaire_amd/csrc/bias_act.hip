@@ -118,14 +118,8 @@ bias_act_bwd_nchw(const T* __restrict__ out, const T* __restrict__ dy, T* __rest
     }
     store_vec<T, VEC>(dx + base + p, g);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int i = 0; i < kThreads / 64; ++i) t += sh[i];
-    partial[(int64_t)n * C + c] = t;
-  }
+  const float t = block_sum<kThreads>(acc, sh);
+  if (threadIdx.x == 0) partial[(int64_t)n * C + c] = t;
 }
 
 // Column sums of a [P, C] fp32 matrix: block = 64 columns x 8 row-groups

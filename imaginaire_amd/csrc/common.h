@@ -90,6 +90,32 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// Sum over a block of T threads of N values per thread, in one fixed order: wave_sum, lane 0 of
+// each wave writes its slot, then thread n < N adds the slots of value n for waves 0 .. T/64-1
+// in that order. Only threads 0 .. N-1 hold a valid result (thread n: the sum of v[n]; with
+// N = 1 that is thread 0 alone); every other thread gets 0. sh: N * T/64 floats of LDS, free
+// for reuse only after a barrier of the caller's. Contains a __syncthreads(): every thread of
+// the block must call it.
+template <int T, int N>
+__device__ __forceinline__ float block_sum(const float (&v)[N], float* sh) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    const float w = wave_sum(v[n]);
+    if ((tid & 63) == 0) sh[n * (T / 64) + (tid >> 6)] = w;
+  }
+  __syncthreads();
+  float s = 0.f;
+  if (tid < N)
+    for (int k = 0; k < T / 64; ++k) s += sh[tid * (T / 64) + k];
+  return s;
+}
+template <int T>
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+  const float one[1] = {v};
+  return block_sum<T, 1>(one, sh);
+}
+
 // Scalars of the spectral-norm weight-gradient formula dW = G / sigma - (<G, W> / sigma^2) u v^T
 // from the <G, W> partial sums dotp[0 .. ndot): summed by every block of T threads itself, in
 // one fixed order (thread-strided, wave shuffle, waves in order). Shared by wgrad_finalize_sn

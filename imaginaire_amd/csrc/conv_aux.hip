@@ -842,15 +842,8 @@ sn_dot_kernel(const __hip_bfloat16* __restrict__ a, const __hip_bfloat16* __rest
     for (int k = 0; k < 8; ++k) acc = fmaf(x[k], y[k], acc);
   }
   __shared__ float red[kT / 64];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < kT / 64; ++k) t += red[k];
-    part[blockIdx.x] = t * (scale ? scale[0] : 1.f);
-  }
+  const float t = block_sum<kT>(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = t * (scale ? scale[0] : 1.f);
 }
 }  // namespace
 

@@ -79,15 +79,8 @@ __global__ void __launch_bounds__(kThreads) l1_partials(const L1Args<T, TB> p, f
   } else {
     for (int64_t j = c0 + threadIdx.x; j < c1; j += kThreads) acc += fabsf(to_f<T>(a[j]) - to_f<TB>(b[j]));
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < kThreads / 64; ++k) s += sh[k];
-    part[bid] = s * p.scale[t];
-  }
+  const float s = block_sum<kThreads>(acc, sh);
+  if (threadIdx.x == 0) part[bid] = s * p.scale[t];
 }
 
 // out[0] = sum of part[0 .. n) in a fixed order (one block)
@@ -96,15 +89,8 @@ __global__ void __launch_bounds__(1024) sum_fixed(const float* __restrict__ part
   __shared__ float sh[1024 / 64];
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += 1024) acc += part[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 1024 / 64; ++k) s += sh[k];
-    out[0] = s;
-  }
+  const float s = block_sum<1024>(acc, sh);
+  if (threadIdx.x == 0) out[0] = s;
 }
 
 template <typename T, typename TB>
@@ -186,15 +172,8 @@ __global__ void __launch_bounds__(kThreads) gan_partials(const GanArgs<T> p, flo
   const float a = p.pa[t], b = p.pb[t];
   float acc = 0.f;
   for (int64_t j = c0 + threadIdx.x; j < c1; j += kThreads) acc += gan_phi(kind, a, b, to_f<T>(x[j]));
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < kThreads / 64; ++k) s += sh[k];
-    part[bid] = s * p.scale[t];
-  }
+  const float s = block_sum<kThreads>(acc, sh);
+  if (threadIdx.x == 0) part[bid] = s * p.scale[t];
 }
 
 template <typename T>

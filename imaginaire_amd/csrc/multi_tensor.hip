@@ -45,6 +45,10 @@ struct Table {
   at::Tensor entries;  // device: TensorEntry[T]
   at::Tensor blocks;   // device: int2 {tensor, chunk} per workgroup
   int nblocks;
+  const TensorEntry* ents() const {
+    return reinterpret_cast<const TensorEntry*>(entries.data_ptr());
+  }
+  const int* blks() const { return blocks.data_ptr<int>(); }
 };
 
 std::mutex g_mu;
@@ -243,21 +247,67 @@ __device__ __forceinline__ void st4(float* __restrict__ p, const float (&i)[4]) 
   else *reinterpret_cast<f32x4*>(p) = v;
 }
 
+// What a workgroup of the block map works on: its tensor's entry and the slice [start, end) of
+// that tensor. start is a multiple of kChunk, so of every vector width used below.
+struct Chunk {
+  TensorEntry e;
+  int t;
+  int64_t start, end;
+};
+__device__ __forceinline__ Chunk block_chunk(const TensorEntry* __restrict__ ents,
+                                             const int* __restrict__ blocks) {
+  const int t = blocks[2 * blockIdx.x], chunk = blocks[2 * blockIdx.x + 1];
+  const TensorEntry e = ents[t];
+  const int64_t start = (int64_t)chunk * kChunk;
+  return {e, t, start, min(e.numel, start + (int64_t)kChunk)};
+}
+
+// The loop of every streaming kernel over its chunk. vec_ok (every operand of the kernel on its
+// vector alignment): groups of 4 elements per lane through load4(i, r) / apply4(i, r), then the
+// last 1..3 elements through apply1(i); otherwise apply1 for every element. V holds one group's
+// registers. U groups per lane per trip, all loads issued before any math: 4 x U 16-B loads in
+// flight per lane and operand (one group at a time left Adam latency-bound at ~1.5 TB/s).
+// kZeroFill: a group past the end is applied as zeros instead of skipped, so apply4 must not
+// touch memory. For a pure reduction (fmaf(0, 0, acc) == acc) that keeps the accumulation one
+// straight chain; branching round the groups cost fromage_norm_kernel 26 VGPRs and two waves of
+// occupancy.
+template <typename V, bool kZeroFill = false, typename Load4, typename Apply4, typename Apply1>
+__device__ __forceinline__ void stream_chunk(const Chunk& c, bool vec_ok, Load4 load4,
+                                             Apply4 apply4, Apply1 apply1) {
+  if (vec_ok) {
+    constexpr int U = 4;
+    const int64_t vend = c.start + ((c.end - c.start) & ~(int64_t)3);
+    for (int64_t base = c.start + threadIdx.x * 4; base < vend; base += kThreads * 4 * U) {
+      V r[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (int64_t)u * kThreads * 4;
+        if (i < vend) load4(i, r[u]);
+        else if (kZeroFill) r[u] = V{};
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + (int64_t)u * kThreads * 4;
+        if (kZeroFill || i < vend) apply4(i, r[u]);
+      }
+    }
+    for (int64_t i = vend + threadIdx.x; i < c.end; i += kThreads) apply1(i);
+  } else {
+    for (int64_t i = c.start + threadIdx.x; i < c.end; i += kThreads) apply1(i);
+  }
+}
+
 template <typename G, bool NT>
 __global__ void __launch_bounds__(kThreads)
 adam_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks, float lr,
             float beta1, float beta2, float eps, float bc1, float bc2, float wd, int adamw,
             float grad_scale, const float* __restrict__ hyper) {
-  const int b = blockIdx.x;
-  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
-  const TensorEntry e = ents[t];
-  float* __restrict__ p = reinterpret_cast<float*>(e.p[0]);
-  const G* __restrict__ g = reinterpret_cast<const G*>(e.p[1]);
-  float* __restrict__ m = reinterpret_cast<float*>(e.p[2]);
-  float* __restrict__ v = reinterpret_cast<float*>(e.p[3]);
-  __hip_bfloat16* __restrict__ shadow = reinterpret_cast<__hip_bfloat16*>(e.p[4]);
-  const int64_t start = (int64_t)chunk * kChunk;
-  const int64_t end = min(e.numel, start + (int64_t)kChunk);
+  const Chunk c = block_chunk(ents, blocks);
+  float* __restrict__ p = reinterpret_cast<float*>(c.e.p[0]);
+  const G* __restrict__ g = reinterpret_cast<const G*>(c.e.p[1]);
+  float* __restrict__ m = reinterpret_cast<float*>(c.e.p[2]);
+  float* __restrict__ v = reinterpret_cast<float*>(c.e.p[3]);
+  __hip_bfloat16* __restrict__ shadow = reinterpret_cast<__hip_bfloat16*>(c.e.p[4]);
   float step_size, rbc2;
   if (hyper) {
     lr = hyper[0];
@@ -267,74 +317,41 @@ adam_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks
     step_size = lr / bc1;
     rbc2 = rsqrtf(bc2);
   }
+  struct V { float p[4], g[4], m[4], v[4]; };
+  auto update = [&](float& pv, float gv, float& mv, float& vv) {
+    float gr = gv * grad_scale;
+    if (!adamw && wd != 0.f) gr = fmaf(wd, pv, gr);
+    mv = fmaf(beta1, mv, (1.f - beta1) * gr);
+    vv = fmaf(beta2, vv, (1.f - beta2) * gr * gr);
+    const float denom = sqrtf(vv) * rbc2 + eps;
+    if (adamw && wd != 0.f) pv *= (1.f - lr * wd);
+    pv -= step_size * mv / denom;
+  };
   // (the shadow, when there is one, is written 4 bf16 = 8 bytes at a time; null passes)
   const bool vec_ok = (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) % 16 == 0) &&
-                      ((uintptr_t)g % (4 * sizeof(G)) == 0) && ((uintptr_t)shadow % 8 == 0) &&
-                      (start % 4 == 0);
-  if (vec_ok) {
-    // U groups of 4 elements per lane per trip, all loads issued before any math: 4 x U 16-B
-    // loads in flight per lane (one group at a time left the kernel latency-bound at ~1.5 TB/s)
-    constexpr int U = 4;
-    for (int64_t base = start + threadIdx.x * 4; base < end; base += kThreads * 4 * U) {
-      float pv[U][4], gv[U][4], mv[U][4], vv[U][4];
-      bool ok[U];
+                      ((uintptr_t)g % (4 * sizeof(G)) == 0) && ((uintptr_t)shadow % 8 == 0);
+  stream_chunk<V>(
+      c, vec_ok,
+      [&](int64_t i, V& r) {
+        ld4<NT>(p + i, r.p);
+        load_vec<G, 4>(g + i, r.g);
+        ld4<NT>(m + i, r.m);
+        ld4<NT>(v + i, r.v);
+      },
+      [&](int64_t i, V& r) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-        ok[u] = i + 3 < end;
-        if (ok[u]) {
-          ld4<NT>(p + i, pv[u]);
-          load_vec<G, 4>(g + i, gv[u]);
-          ld4<NT>(m + i, mv[u]);
-          ld4<NT>(v + i, vv[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (!ok[u]) continue;
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float gr = gv[u][k] * grad_scale;
-          if (!adamw && wd != 0.f) gr = fmaf(wd, pv[u][k], gr);
-          mv[u][k] = fmaf(beta1, mv[u][k], (1.f - beta1) * gr);
-          vv[u][k] = fmaf(beta2, vv[u][k], (1.f - beta2) * gr * gr);
-          const float denom = sqrtf(vv[u][k]) * rbc2 + eps;
-          if (adamw && wd != 0.f) pv[u][k] *= (1.f - lr * wd);
-          pv[u][k] -= step_size * mv[u][k] / denom;
-        }
-        st4<NT>(p + i, pv[u]);
-        st4<NT>(m + i, mv[u]);
-        st4<NT>(v + i, vv[u]);
-        if (shadow) store_vec<__hip_bfloat16, 4>(shadow + i, pv[u]);
-      }
-    }
-    // tail (numel not multiple of 4)
-    const int64_t tail0 = start + ((end - start) / 4) * 4;
-    for (int64_t i = tail0 + threadIdx.x; i < end; i += kThreads) {
-      float gr = to_f<G>(g[i]) * grad_scale;
-      float pv = p[i];
-      if (!adamw && wd != 0.f) gr = fmaf(wd, pv, gr);
-      float mv = fmaf(beta1, m[i], (1.f - beta1) * gr);
-      float vv = fmaf(beta2, v[i], (1.f - beta2) * gr * gr);
-      if (adamw && wd != 0.f) pv *= (1.f - lr * wd);
-      pv -= step_size * mv / (sqrtf(vv) * rbc2 + eps);
-      p[i] = pv; m[i] = mv; v[i] = vv;
-      if (shadow) shadow[i] = __float2bfloat16(pv);
-    }
-  } else {
-    for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
-      float gr = to_f<G>(g[i]) * grad_scale;
-      float pv = p[i];
-      if (!adamw && wd != 0.f) gr = fmaf(wd, pv, gr);
-      float mv = fmaf(beta1, m[i], (1.f - beta1) * gr);
-      float vv = fmaf(beta2, v[i], (1.f - beta2) * gr * gr);
-      if (adamw && wd != 0.f) pv *= (1.f - lr * wd);
-      pv -= step_size * mv / (sqrtf(vv) * rbc2 + eps);
-      p[i] = pv; m[i] = mv; v[i] = vv;
-      if (shadow) shadow[i] = __float2bfloat16(pv);
-    }
-  }
+        for (int k = 0; k < 4; ++k) update(r.p[k], r.g[k], r.m[k], r.v[k]);
+        st4<NT>(p + i, r.p);
+        st4<NT>(m + i, r.m);
+        st4<NT>(v + i, r.v);
+        if (shadow) store_vec<__hip_bfloat16, 4>(shadow + i, r.p);
+      },
+      [&](int64_t i) {
+        float pv = p[i], mv = m[i], vv = v[i];
+        update(pv, to_f<G>(g[i]), mv, vv);
+        p[i] = pv; m[i] = mv; v[i] = vv;
+        if (shadow) shadow[i] = __float2bfloat16(pv);
+      });
 }
 
 // σ_i = Σ_{r,c} u[r] W[r,c] v[c]  (W viewed as [rows, numel/rows]); one partial per chunk.
@@ -343,17 +360,14 @@ __global__ void __launch_bounds__(kThreads)
 sn_sigma_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks,
                 float* __restrict__ part) {
   __shared__ float sh[kThreads / 64];
-  const int b = blockIdx.x;
-  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
-  const TensorEntry e = ents[t];
-  const float* __restrict__ W = reinterpret_cast<const float*>(e.p[0]);
-  const float* __restrict__ u = reinterpret_cast<const float*>(e.p[1]);
+  const Chunk ch = block_chunk(ents, blocks);
+  const float* __restrict__ W = reinterpret_cast<const float*>(ch.e.p[0]);
+  const float* __restrict__ u = reinterpret_cast<const float*>(ch.e.p[1]);
   // p[3]: v permuted to the weight's MEMORY column order by sn_vperm (coalesced reads; the
   // logical-order v of a channels-last conv weight would be a stride-KH*KW gather)
-  const float* __restrict__ v = reinterpret_cast<const float*>(e.p[3]);
-  const int64_t ncol = e.cols;
-  const int64_t start = (int64_t)chunk * kChunk;
-  const int64_t end = min(e.numel, start + (int64_t)kChunk);
+  const float* __restrict__ v = reinterpret_cast<const float*>(ch.e.p[3]);
+  const int64_t ncol = ch.e.cols;
+  const int64_t start = ch.start, end = ch.end;
   float acc = 0.f;
   if ((ncol & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(v) & 15) == 0) {
@@ -380,35 +394,31 @@ sn_sigma_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ bl
       while (c >= ncol) { c -= ncol; ++r; }
     }
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int k = 0; k < kThreads / 64; ++k) s += sh[k];
-    part[b] = s;  // per-workgroup partial; reduce_block_partials sums them in a fixed order
-  }
+  // per-workgroup partial; reduce_block_partials sums them in a fixed order
+  const float s = block_sum<kThreads>(acc, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// out[t] = Σ_{b : blocks[b].tensor == t} part[b], one workgroup per tensor (T = 1 with
-// all_blocks: every partial). Fixed per-thread strides + a fixed tree: bitwise reproducible,
-// unlike one float atomic per workgroup (whose arrival order varies run to run).
+// out[t][n] = Σ_{b : blocks[b].tensor == t} part[b][n] for the N values per workgroup, one
+// workgroup per tensor (T = 1 with all_blocks: every partial). Fixed per-thread strides + a
+// fixed tree: bitwise reproducible, unlike one float atomic per workgroup (whose arrival order
+// varies run to run).
+template <int N>
 __global__ void __launch_bounds__(kThreads)
 reduce_block_partials(const float* __restrict__ part, const int* __restrict__ blocks, int nblocks,
                       bool all_blocks, float* __restrict__ out) {
-  __shared__ float sh[kThreads / 64];
+  __shared__ float sh[N * (kThreads / 64)];
   const int t = blockIdx.x;
-  float acc = 0.f;
+  float acc[N];
+#pragma unroll
+  for (int n = 0; n < N; ++n) acc[n] = 0.f;
   for (int b = threadIdx.x; b < nblocks; b += kThreads)
-    if (all_blocks || blocks[2 * b] == t) acc += part[b];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int k = 0; k < kThreads / 64; ++k) s += sh[k];
-    out[t] = s;
-  }
+    if (all_blocks || blocks[2 * b] == t) {
+#pragma unroll
+      for (int n = 0; n < N; ++n) acc[n] += part[N * b + n];
+    }
+  const float s = block_sum<kThreads, N>(acc, sh);
+  if (threadIdx.x < N) out[N * t + threadIdx.x] = s;
 }
 
 // one block per tensor: vm[c] = v[logical(c)] for every memory column c
@@ -428,73 +438,52 @@ sn_vperm(const TensorEntry* __restrict__ ents) {
   }
 }
 
-// t = beta*t + (1-beta)*s*scale[t_idx]; p0 = target, p1 = source (same dtype: fp32).
-// NT: the average itself is streamed (non-temporal fp32 load / store: nothing else in the step
-// reads it): 0.962 -> 0.928 ms for 415M parameters (profiles/ema_nt_ab_r6_mi355x.txt);
-// IMAGINAIRE_AMD_EMA_NT=0 switches back to plain accesses.
+// t = beta*t + (1-beta)*s*scale[t_idx]; p0 = target, p1 = source (same dtype).
+// The 16-B path is for fp32 only. NT: the average itself is streamed (non-temporal fp32 load /
+// store: nothing else in the step reads it): 0.962 -> 0.928 ms for 415M parameters
+// (profiles/ema_nt_ab_r6_mi355x.txt); IMAGINAIRE_AMD_EMA_NT=0 switches back to plain accesses.
 template <typename T, bool NT>
 __global__ void __launch_bounds__(kThreads)
 ema_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks, float beta,
            const float* __restrict__ inv_scale, const int64_t* __restrict__ count,
            int64_t warm_until) {
-  const int b = blockIdx.x;
-  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
-  const TensorEntry e = ents[t];
+  const Chunk c = block_chunk(ents, blocks);
   // device-side warm-up switch (model_average.py: beta = 0 until start_iteration), so a
   // replayed hipGraph turns the average on at the right iteration
   if (count && *count <= warm_until) beta = 0.f;
-  T* __restrict__ dst = reinterpret_cast<T*>(e.p[0]);
-  const T* __restrict__ src = reinterpret_cast<const T*>(e.p[1]);
-  const float sc = inv_scale ? 1.f / inv_scale[t] : 1.f;
+  T* __restrict__ dst = reinterpret_cast<T*>(c.e.p[0]);
+  const T* __restrict__ src = reinterpret_cast<const T*>(c.e.p[1]);
+  const float sc = inv_scale ? 1.f / inv_scale[c.t] : 1.f;
   const float a = 1.f - beta;
-  const int64_t start = (int64_t)chunk * kChunk;
-  const int64_t end = min(e.numel, start + (int64_t)kChunk);
   const float as = a * sc;
-  if (sizeof(T) == 4 && (((uintptr_t)dst | (uintptr_t)src) & 15) == 0) {
-    // 16-B accesses, U groups per lane per trip with every load issued first
-    constexpr int U = 4;
-    const int64_t vend = start + ((end - start) & ~(int64_t)3);
-    for (int64_t base = start + threadIdx.x * 4; base < vend; base += kThreads * 4 * U) {
-      float dv[U][4], sv[U][4];
+  struct V { float d[4], s[4]; };
+  auto update = [&](float dv, float sv) { return fmaf(beta, dv, as * sv); };
+  const bool vec_ok = sizeof(T) == 4 && (((uintptr_t)dst | (uintptr_t)src) & 15) == 0;
+  stream_chunk<V>(
+      c, vec_ok,
+      [&](int64_t i, V& r) {
+        if constexpr (std::is_same<T, float>::value) ld4<NT>(dst + i, r.d);
+        else load_vec<T, 4>(dst + i, r.d);
+        load_vec<T, 4>(src + i, r.s);
+      },
+      [&](int64_t i, V& r) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-        if (i < vend) {
-          if constexpr (std::is_same<T, float>::value) ld4<NT>(dst + i, dv[u]);
-          else load_vec<T, 4>(dst + i, dv[u]);
-          load_vec<T, 4>(src + i, sv[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-        if (i >= vend) continue;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dv[u][k] = fmaf(beta, dv[u][k], as * sv[u][k]);
-        if constexpr (std::is_same<T, float>::value) st4<NT>(dst + i, dv[u]);
-        else store_vec<T, 4>(dst + i, dv[u]);
-      }
-    }
-    for (int64_t i = vend + threadIdx.x; i < end; i += kThreads)
-      dst[i] = from_f<T>(fmaf(beta, to_f<T>(dst[i]), as * to_f<T>(src[i])));
-    return;
-  }
-  for (int64_t i = start + threadIdx.x; i < end; i += kThreads)
-    dst[i] = from_f<T>(fmaf(beta, to_f<T>(dst[i]), as * to_f<T>(src[i])));
+        for (int k = 0; k < 4; ++k) r.d[k] = update(r.d[k], r.s[k]);
+        if constexpr (std::is_same<T, float>::value) st4<NT>(dst + i, r.d);
+        else store_vec<T, 4>(dst + i, r.d);
+      },
+      [&](int64_t i) { dst[i] = from_f<T>(update(to_f<T>(dst[i]), to_f<T>(src[i]))); });
 }
 
 template <typename T>
 __global__ void __launch_bounds__(kThreads)
 scale_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks,
              const float* __restrict__ s) {
-  const int b = blockIdx.x;
-  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
-  const TensorEntry e = ents[t];
-  T* __restrict__ x = reinterpret_cast<T*>(e.p[0]);
+  const Chunk c = block_chunk(ents, blocks);
+  T* __restrict__ x = reinterpret_cast<T*>(c.e.p[0]);
   const float f = *s;
-  const int64_t start = (int64_t)chunk * kChunk;
-  const int64_t end = min(e.numel, start + (int64_t)kChunk);
-  for (int64_t i = start + threadIdx.x; i < end; i += kThreads) x[i] = from_f<T>(to_f<T>(x[i]) * f);
+  for (int64_t i = c.start + threadIdx.x; i < c.end; i += kThreads)
+    x[i] = from_f<T>(to_f<T>(x[i]) * f);
 }
 
 template <typename T>
@@ -502,124 +491,51 @@ __global__ void __launch_bounds__(kThreads)
 sqnorm_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks,
               float* __restrict__ part) {
   __shared__ float sh[kThreads / 64];
-  const int b = blockIdx.x;
-  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
-  const TensorEntry e = ents[t];
-  const T* __restrict__ x = reinterpret_cast<const T*>(e.p[0]);
-  const int64_t start = (int64_t)chunk * kChunk;
-  const int64_t end = min(e.numel, start + (int64_t)kChunk);
+  const Chunk c = block_chunk(ents, blocks);
+  const T* __restrict__ x = reinterpret_cast<const T*>(c.e.p[0]);
   float acc = 0.f;
-  for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
+  for (int64_t i = c.start + threadIdx.x; i < c.end; i += kThreads) {
     const float v = to_f<T>(x[i]);
     acc = fmaf(v, v, acc);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int k = 0; k < kThreads / 64; ++k) s += sh[k];
-    part[b] = s;
-  }
+  const float s = block_sum<kThreads>(acc, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 // ---- Fromage / Madam (reference optimizers/fromage.py, optimizers/madam.py) --------------------
-// Both follow adam_kernel's chunking: one kChunk slice per workgroup, a 16-byte vector body with
-// U groups of loads in flight per lane, a scalar tail for the last 1..3 elements and a scalar
-// fallback when an operand is off the vector alignment. Everything a step decides (Fromage's
-// zero-norm branch, Madam's bias correction and clamp bound) is decided on the device, so the
-// step records into a hipGraph as it is.
+// Everything a step decides (Fromage's zero-norm branch, Madam's bias correction and clamp bound)
+// is decided on the device, so the step records into a hipGraph as it is. Their fp32 operands
+// are always streamed (non-temporal).
 
 // Fromage pass 1: part[b] = {Σ p², Σ g²} over workgroup b's chunk. p0 = p (fp32), p1 = g.
 template <typename G>
 __global__ void __launch_bounds__(kThreads)
 fromage_norm_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks,
                     float* __restrict__ part) {
-  __shared__ float sh[2][kThreads / 64];
-  const int b = blockIdx.x;
-  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
-  const TensorEntry e = ents[t];
-  const float* __restrict__ p = reinterpret_cast<const float*>(e.p[0]);
-  const G* __restrict__ g = reinterpret_cast<const G*>(e.p[1]);
-  const int64_t start = (int64_t)chunk * kChunk;
-  const int64_t end = min(e.numel, start + (int64_t)kChunk);
-  float ap = 0.f, ag = 0.f;
+  __shared__ float sh[2 * (kThreads / 64)];
+  const Chunk c = block_chunk(ents, blocks);
+  const float* __restrict__ p = reinterpret_cast<const float*>(c.e.p[0]);
+  const G* __restrict__ g = reinterpret_cast<const G*>(c.e.p[1]);
+  float acc[2] = {0.f, 0.f};  // {Σ p², Σ g²} of this lane
+  struct V { float p[4], g[4]; };
+  auto update = [&](float pv, float gv) {
+    acc[0] = fmaf(pv, pv, acc[0]);
+    acc[1] = fmaf(gv, gv, acc[1]);
+  };
   const bool vec_ok = ((uintptr_t)p % 16 == 0) && ((uintptr_t)g % (4 * sizeof(G)) == 0);
-  if (vec_ok) {
-    constexpr int U = 4;
-    const int64_t vend = start + ((end - start) & ~(int64_t)3);
-    for (int64_t base = start + threadIdx.x * 4; base < vend; base += kThreads * 4 * U) {
-      float pv[U][4], gv[U][4];
+  stream_chunk<V, /*kZeroFill=*/true>(
+      c, vec_ok,
+      [&](int64_t i, V& r) {
+        ld4<true>(p + i, r.p);
+        load_vec<G, 4>(g + i, r.g);
+      },
+      [&](int64_t, V& r) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-        if (i < vend) {
-          ld4<true>(p + i, pv[u]);
-          load_vec<G, 4>(g + i, gv[u]);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) pv[u][k] = gv[u][k] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          ap = fmaf(pv[u][k], pv[u][k], ap);
-          ag = fmaf(gv[u][k], gv[u][k], ag);
-        }
-    }
-    for (int64_t i = vend + threadIdx.x; i < end; i += kThreads) {
-      const float pv = p[i], gv = to_f<G>(g[i]);
-      ap = fmaf(pv, pv, ap);
-      ag = fmaf(gv, gv, ag);
-    }
-  } else {
-    for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
-      const float pv = p[i], gv = to_f<G>(g[i]);
-      ap = fmaf(pv, pv, ap);
-      ag = fmaf(gv, gv, ag);
-    }
-  }
-  ap = wave_sum(ap);
-  ag = wave_sum(ag);
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = ap;
-    sh[1][threadIdx.x >> 6] = ag;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    float s = 0.f;
-    for (int k = 0; k < kThreads / 64; ++k) s += sh[threadIdx.x][k];
-    part[2 * b + threadIdx.x] = s;
-  }
-}
-
-// Two-output sibling of reduce_block_partials: out[t] = {Σ part[b][0], Σ part[b][1]} over the
-// workgroups of tensor t, one workgroup per tensor, in one fixed order.
-__global__ void __launch_bounds__(kThreads)
-reduce_block_partials2(const float* __restrict__ part, const int* __restrict__ blocks,
-                       int nblocks, float* __restrict__ out) {
-  __shared__ float sh[2][kThreads / 64];
-  const int t = blockIdx.x;
-  float a0 = 0.f, a1 = 0.f;
-  for (int b = threadIdx.x; b < nblocks; b += kThreads)
-    if (blocks[2 * b] == t) {
-      a0 += part[2 * b];
-      a1 += part[2 * b + 1];
-    }
-  a0 = wave_sum(a0);
-  a1 = wave_sum(a1);
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = a0;
-    sh[1][threadIdx.x >> 6] = a1;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    float s = 0.f;
-    for (int k = 0; k < kThreads / 64; ++k) s += sh[threadIdx.x][k];
-    out[2 * t + threadIdx.x] = s;
-  }
+        for (int k = 0; k < 4; ++k) update(r.p[k], r.g[k]);
+      },
+      [&](int64_t i) { update(p[i], to_f<G>(g[i])); });
+  const float s = block_sum<kThreads, 2>(acc, sh);
+  if (threadIdx.x < 2) part[2 * blockIdx.x + threadIdx.x] = s;
 }
 
 // Fromage pass 2: p = (p - lr * ratio * g) / sqrt(1 + lr²), ratio = |p| / |g| of the whole
@@ -628,59 +544,39 @@ template <typename G>
 __global__ void __launch_bounds__(kThreads)
 fromage_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks,
                const float* __restrict__ norms, float lr, const float* __restrict__ hyper) {
-  const int b = blockIdx.x;
-  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
-  const TensorEntry e = ents[t];
-  float* __restrict__ p = reinterpret_cast<float*>(e.p[0]);
-  const G* __restrict__ g = reinterpret_cast<const G*>(e.p[1]);
-  __hip_bfloat16* __restrict__ shadow = reinterpret_cast<__hip_bfloat16*>(e.p[2]);
-  const int64_t start = (int64_t)chunk * kChunk;
-  const int64_t end = min(e.numel, start + (int64_t)kChunk);
+  const Chunk ch = block_chunk(ents, blocks);
+  float* __restrict__ p = reinterpret_cast<float*>(ch.e.p[0]);
+  const G* __restrict__ g = reinterpret_cast<const G*>(ch.e.p[1]);
+  __hip_bfloat16* __restrict__ shadow = reinterpret_cast<__hip_bfloat16*>(ch.e.p[2]);
   if (hyper) lr = hyper[0];
-  const float pn = sqrtf(norms[2 * t]), gn = sqrtf(norms[2 * t + 1]);
+  const float pn = sqrtf(norms[2 * ch.t]), gn = sqrtf(norms[2 * ch.t + 1]);
   const float na = -lr * ((pn > 0.f && gn > 0.f) ? pn / gn : 1.f);
   const float c = 1.f / sqrtf(fmaf(lr, lr, 1.f));
+  struct V { float p[4], g[4]; };
+  auto update = [&](float pv, float gv) { return fmaf(na, gv, pv) * c; };
   const bool vec_ok = ((uintptr_t)p % 16 == 0) && ((uintptr_t)g % (4 * sizeof(G)) == 0) &&
                       ((uintptr_t)shadow % 8 == 0);
-  if (vec_ok) {
-    constexpr int U = 4;
-    const int64_t vend = start + ((end - start) & ~(int64_t)3);
-    for (int64_t base = start + threadIdx.x * 4; base < vend; base += kThreads * 4 * U) {
-      float pv[U][4], gv[U][4];
+  stream_chunk<V>(
+      ch, vec_ok,
+      [&](int64_t i, V& r) {
+        ld4<true>(p + i, r.p);
+        load_vec<G, 4>(g + i, r.g);
+      },
+      [&](int64_t i, V& r) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-        if (i < vend) {
-          ld4<true>(p + i, pv[u]);
-          load_vec<G, 4>(g + i, gv[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-        if (i >= vend) continue;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) pv[u][k] = fmaf(na, gv[u][k], pv[u][k]) * c;
-        st4<true>(p + i, pv[u]);
-        if (shadow) store_vec<__hip_bfloat16, 4>(shadow + i, pv[u]);
-      }
-    }
-    for (int64_t i = vend + threadIdx.x; i < end; i += kThreads) {
-      const float pv = fmaf(na, to_f<G>(g[i]), p[i]) * c;
-      p[i] = pv;
-      if (shadow) shadow[i] = __float2bfloat16(pv);
-    }
-  } else {
-    for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
-      const float pv = fmaf(na, to_f<G>(g[i]), p[i]) * c;
-      p[i] = pv;
-      if (shadow) shadow[i] = __float2bfloat16(pv);
-    }
-  }
+        for (int k = 0; k < 4; ++k) r.p[k] = update(r.p[k], r.g[k]);
+        st4<true>(p + i, r.p);
+        if (shadow) store_vec<__hip_bfloat16, 4>(shadow + i, r.p);
+      },
+      [&](int64_t i) {
+        const float pv = update(p[i], to_f<G>(g[i]));
+        p[i] = pv;
+        if (shadow) shadow[i] = __float2bfloat16(pv);
+      });
 }
 
-// Madam's per-parameter device state is {step, max} (fp32, table slot p4).
-// state[1] = scale * sqrt(mean(p²)) from the per-tensor Σ p² (p0 = p, p1 = state).
+// Madam's per-parameter device state is {step, max} (fp32): slot p1 of mt_madam_init's table,
+// slot p4 of mt_madam's. Here: state[1] = scale * sqrt(mean(p²)) from the per-tensor Σ p².
 __global__ void __launch_bounds__(kThreads)
 madam_max_kernel(const TensorEntry* __restrict__ ents, int ntensors,
                  const float* __restrict__ sums, float scale) {
@@ -719,63 +615,41 @@ template <typename G>
 __global__ void __launch_bounds__(kThreads)
 madam_kernel(const TensorEntry* __restrict__ ents, const int* __restrict__ blocks, float lr,
              float bound, const float* __restrict__ hyper) {
-  const int b = blockIdx.x;
-  const int t = blocks[2 * b], chunk = blocks[2 * b + 1];
-  const TensorEntry e = ents[t];
-  float* __restrict__ p = reinterpret_cast<float*>(e.p[0]);
-  const G* __restrict__ g = reinterpret_cast<const G*>(e.p[1]);
-  float* __restrict__ v = reinterpret_cast<float*>(e.p[2]);
-  __hip_bfloat16* __restrict__ shadow = reinterpret_cast<__hip_bfloat16*>(e.p[3]);
-  const float* __restrict__ st = reinterpret_cast<const float*>(e.p[4]);
-  const int64_t start = (int64_t)chunk * kChunk;
-  const int64_t end = min(e.numel, start + (int64_t)kChunk);
+  const Chunk c = block_chunk(ents, blocks);
+  float* __restrict__ p = reinterpret_cast<float*>(c.e.p[0]);
+  const G* __restrict__ g = reinterpret_cast<const G*>(c.e.p[1]);
+  float* __restrict__ v = reinterpret_cast<float*>(c.e.p[2]);
+  __hip_bfloat16* __restrict__ shadow = reinterpret_cast<__hip_bfloat16*>(c.e.p[3]);
+  const float* __restrict__ st = reinterpret_cast<const float*>(c.e.p[4]);
   if (hyper) lr = hyper[0];
   const float nlr = -lr;
   // once per workgroup: bc = 1 - 0.999^step = -expm1(step * ln 0.999) (the form that keeps its
   // precision at small step counts, where 0.999^step is close to 1)
   const float sbc = sqrtf(-expm1f(st[0] * -1.0005003335835335e-3f));
   const float mx = st[1];
+  struct V { float p[4], g[4], v[4]; };
   const bool vec_ok = (((uintptr_t)p | (uintptr_t)v) % 16 == 0) &&
                       ((uintptr_t)g % (4 * sizeof(G)) == 0) && ((uintptr_t)shadow % 8 == 0);
-  if (vec_ok) {
-    constexpr int U = 4;
-    const int64_t vend = start + ((end - start) & ~(int64_t)3);
-    for (int64_t base = start + threadIdx.x * 4; base < vend; base += kThreads * 4 * U) {
-      float pv[U][4], gv[U][4], vv[U][4];
+  stream_chunk<V>(
+      c, vec_ok,
+      [&](int64_t i, V& r) {
+        ld4<true>(p + i, r.p);
+        load_vec<G, 4>(g + i, r.g);
+        ld4<true>(v + i, r.v);
+      },
+      [&](int64_t i, V& r) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-        if (i < vend) {
-          ld4<true>(p + i, pv[u]);
-          load_vec<G, 4>(g + i, gv[u]);
-          ld4<true>(v + i, vv[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * kThreads * 4;
-        if (i >= vend) continue;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) madam_update(pv[u][k], gv[u][k], vv[u][k], sbc, nlr, bound, mx);
-        st4<true>(v + i, vv[u]);
-        st4<true>(p + i, pv[u]);
-        if (shadow) store_vec<__hip_bfloat16, 4>(shadow + i, pv[u]);
-      }
-    }
-    for (int64_t i = vend + threadIdx.x; i < end; i += kThreads) {
-      float pv = p[i], vv = v[i];
-      madam_update(pv, to_f<G>(g[i]), vv, sbc, nlr, bound, mx);
-      v[i] = vv; p[i] = pv;
-      if (shadow) shadow[i] = __float2bfloat16(pv);
-    }
-  } else {
-    for (int64_t i = start + threadIdx.x; i < end; i += kThreads) {
-      float pv = p[i], vv = v[i];
-      madam_update(pv, to_f<G>(g[i]), vv, sbc, nlr, bound, mx);
-      v[i] = vv; p[i] = pv;
-      if (shadow) shadow[i] = __float2bfloat16(pv);
-    }
-  }
+        for (int k = 0; k < 4; ++k) madam_update(r.p[k], r.g[k], r.v[k], sbc, nlr, bound, mx);
+        st4<true>(v + i, r.v);
+        st4<true>(p + i, r.p);
+        if (shadow) store_vec<__hip_bfloat16, 4>(shadow + i, r.p);
+      },
+      [&](int64_t i) {
+        float pv = p[i], vv = v[i];
+        madam_update(pv, to_f<G>(g[i]), vv, sbc, nlr, bound, mx);
+        v[i] = vv; p[i] = pv;
+        if (shadow) shadow[i] = __float2bfloat16(pv);
+      });
 }
 
 void check_same_dtype(const std::vector<at::Tensor>& l, at::ScalarType st, const char* what) {
@@ -783,6 +657,49 @@ void check_same_dtype(const std::vector<at::Tensor>& l, at::ScalarType st, const
     IAMD_CHECK(t.scalar_type() == st, what, ": dtype mismatch");
     IAMD_CHECK(t.is_non_overlapping_and_dense(), what, ": tensors must be dense");
   }
+}
+
+// The device hyper-parameters of an optimizer step, learning rate first: a replayed graph sees
+// a changed value. Null = none given, use the host arguments.
+float* lr_hyper(const c10::optional<at::Tensor>& hyper, const char* what, int64_t min_numel = 1) {
+  if (!hyper.has_value() || !hyper->defined()) return nullptr;
+  IAMD_CHECK(hyper->is_cuda() && hyper->scalar_type() == at::kFloat &&
+                 hyper->numel() >= min_numel && hyper->is_contiguous(),
+             what, ": hyper must be a contiguous fp32 device tensor [lr, ...] of at least ",
+             min_numel, " floats");
+  return hyper->data_ptr<float>();
+}
+
+// Optional bf16 shadows, one per parameter (an empty tensor = none for that parameter); an empty
+// list = none at all, returned as a list of empty tensors so the table slots stay put.
+std::vector<at::Tensor> shadow_list(const std::vector<at::Tensor>& shadows,
+                                    const std::vector<at::Tensor>& params, const char* what) {
+  if (shadows.empty())
+    return std::vector<at::Tensor>(params.size(),
+                                   at::empty({0}, params[0].options().dtype(at::kBFloat16)));
+  IAMD_CHECK(shadows.size() == params.size(), what, ": shadow list size");
+  for (size_t i = 0; i < shadows.size(); ++i) {
+    if (shadows[i].numel() == 0) continue;
+    IAMD_CHECK(shadows[i].scalar_type() == at::kBFloat16 && shadows[i].is_cuda() &&
+                   shadows[i].sizes() == params[i].sizes() &&
+                   shadows[i].strides() == params[i].strides(),
+               what, ": a shadow must be a bf16 tensor laid out like its parameter");
+  }
+  return shadows;
+}
+
+// fn(tag) with a null pointer of the gradients' element type
+template <typename F>
+void dispatch_grad(at::ScalarType gdt, const char* name, F fn) {
+  if (gdt == at::kFloat) fn(static_cast<float*>(nullptr));
+  else if (gdt == at::kBFloat16) fn(static_cast<__hip_bfloat16*>(nullptr));
+  else IAMD_CHECK(false, name, ": grads must be fp32 or bf16");
+}
+
+// A switch that is on unless the environment variable starts with 0.
+bool env_default_on(const char* name) {
+  const char* e = std::getenv(name);
+  return !(e && e[0] == '0');
 }
 
 }  // namespace
@@ -801,13 +718,7 @@ void mt_adam(const std::vector<at::Tensor>& params, const std::vector<at::Tensor
              double eps, int64_t step, double weight_decay, bool adamw, double grad_scale,
              const c10::optional<at::Tensor>& hyper) {
   if (params.empty()) return;
-  float* hp = nullptr;
-  if (hyper.has_value() && hyper->defined()) {
-    IAMD_CHECK(hyper->is_cuda() && hyper->scalar_type() == at::kFloat && hyper->numel() == 4 &&
-                   hyper->is_contiguous(),
-               "mt_adam: hyper must be a contiguous fp32 device tensor [lr, step, ., .]");
-    hp = hyper->data_ptr<float>();
-  }
+  float* hp = lr_hyper(hyper, "mt_adam", 4);  // [lr, step, step_size, rsqrt(bc2)]
   IAMD_CHECK(params.size() == grads.size() && params.size() == exp_avgs.size() &&
                  params.size() == exp_avg_sqs.size(),
              "mt_adam: list sizes differ");
@@ -816,45 +727,21 @@ void mt_adam(const std::vector<at::Tensor>& params, const std::vector<at::Tensor
   check_same_dtype(exp_avg_sqs, at::kFloat, "mt_adam exp_avg_sq");
   const auto gdt = grads[0].scalar_type();
   check_same_dtype(grads, gdt, "mt_adam grads");
-  std::vector<std::vector<at::Tensor>> lists{params, grads, exp_avgs, exp_avg_sqs};
-  if (!shadows.empty()) {
-    // optional per parameter: an empty tensor = no shadow for that parameter
-    IAMD_CHECK(shadows.size() == params.size(), "mt_adam: shadow list size");
-    for (size_t i = 0; i < shadows.size(); ++i) {
-      if (shadows[i].numel() == 0) continue;
-      IAMD_CHECK(shadows[i].scalar_type() == at::kBFloat16 && shadows[i].is_cuda() &&
-                     shadows[i].sizes() == params[i].sizes() &&
-                     shadows[i].strides() == params[i].strides(),
-                 "mt_adam: a shadow must be a bf16 tensor laid out like its parameter");
-    }
-    lists.push_back(shadows);
-  }
-  Table& tb = get_table(lists, params[0].device());
+  Table& tb = get_table({params, grads, exp_avgs, exp_avg_sqs,
+                         shadow_list(shadows, params, "mt_adam")}, params[0].device());
   const float bc1 = 1.f - (float)std::pow(beta1, (double)step);
   const float bc2 = 1.f - (float)std::pow(beta2, (double)step);
-  auto ents = reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr());
-  auto blks = tb.blocks.data_ptr<int>();
   if (hp)
     hipLaunchKernelGGL(adam_hyper_step, dim3(1), dim3(64), 0, stream(), hp, (float)beta1,
                        (float)beta2);
-  static const bool nt = [] {
-    const char* e = std::getenv("IMAGINAIRE_AMD_ADAM_NT");
-    return !(e && e[0] == '0');
-  }();
-#define IAMD_ADAM_LAUNCH(G, NT)                                                              \
-  hipLaunchKernelGGL((adam_kernel<G, NT>), dim3(tb.nblocks), dim3(kThreads), 0, stream(), ents, \
-                     blks, (float)lr, (float)beta1, (float)beta2, (float)eps, bc1, bc2,        \
-                     (float)weight_decay, adamw ? 1 : 0, (float)grad_scale, hp)
-  if (gdt == at::kFloat) {
-    if (nt) IAMD_ADAM_LAUNCH(float, true);
-    else IAMD_ADAM_LAUNCH(float, false);
-  } else if (gdt == at::kBFloat16) {
-    if (nt) IAMD_ADAM_LAUNCH(__hip_bfloat16, true);
-    else IAMD_ADAM_LAUNCH(__hip_bfloat16, false);
-  }
-#undef IAMD_ADAM_LAUNCH
-  else
-    IAMD_CHECK(false, "mt_adam: grads must be fp32 or bf16");
+  static const bool nt = env_default_on("IMAGINAIRE_AMD_ADAM_NT");
+  dispatch_grad(gdt, "mt_adam", [&](auto tag) {
+    using G = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL((nt ? adam_kernel<G, true> : adam_kernel<G, false>), dim3(tb.nblocks),
+                       dim3(kThreads), 0, stream(), tb.ents(), tb.blks(), (float)lr, (float)beta1,
+                       (float)beta2, (float)eps, bc1, bc2, (float)weight_decay, adamw ? 1 : 0,
+                       (float)grad_scale, hp);
+  });
   IAMD_LAUNCH_CHECK();
 }
 
@@ -892,13 +779,12 @@ at::Tensor mt_sn_sigma(const std::vector<at::Tensor>& weights, const std::vector
   auto sigma = at::empty({(int64_t)weights.size()}, weights[0].options());
   auto part = at::empty({(int64_t)tb.nblocks}, weights[0].options());
   hipLaunchKernelGGL(sn_vperm, dim3((unsigned)weights.size()), dim3(kThreads), 0, stream(),
-                     reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr()));
-  hipLaunchKernelGGL(sn_sigma_kernel, dim3(tb.nblocks), dim3(kThreads), 0, stream(),
-                     reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr()),
-                     tb.blocks.data_ptr<int>(), part.data_ptr<float>());
-  hipLaunchKernelGGL(reduce_block_partials, dim3((unsigned)weights.size()), dim3(kThreads), 0,
-                     stream(), part.data_ptr<float>(), tb.blocks.data_ptr<int>(), tb.nblocks,
-                     false, sigma.data_ptr<float>());
+                     tb.ents());
+  hipLaunchKernelGGL(sn_sigma_kernel, dim3(tb.nblocks), dim3(kThreads), 0, stream(), tb.ents(),
+                     tb.blks(), part.data_ptr<float>());
+  hipLaunchKernelGGL(reduce_block_partials<1>, dim3((unsigned)weights.size()), dim3(kThreads), 0,
+                     stream(), part.data_ptr<float>(), tb.blks(), tb.nblocks, false,
+                     sigma.data_ptr<float>());
   IAMD_LAUNCH_CHECK();
   return sigma;
 }
@@ -923,18 +809,11 @@ void mt_ema(const std::vector<at::Tensor>& targets, const std::vector<at::Tensor
                "mt_ema: sigma must be fp32 [T]");
     sp = sigma->data_ptr<float>();
   }
-  static const bool nt = [] {
-    const char* e = std::getenv("IMAGINAIRE_AMD_EMA_NT");
-    return !(e && e[0] == '0');
-  }();
+  static const bool nt = env_default_on("IMAGINAIRE_AMD_EMA_NT");
   IAMD_DISPATCH_FLOAT_TYPES(dt, "mt_ema", [&] {
-    auto ents = reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr());
-    if (nt)
-      hipLaunchKernelGGL((ema_kernel<scalar_t, true>), dim3(tb.nblocks), dim3(kThreads), 0,
-                         stream(), ents, tb.blocks.data_ptr<int>(), (float)beta, sp, cp, start);
-    else
-      hipLaunchKernelGGL((ema_kernel<scalar_t, false>), dim3(tb.nblocks), dim3(kThreads), 0,
-                         stream(), ents, tb.blocks.data_ptr<int>(), (float)beta, sp, cp, start);
+    hipLaunchKernelGGL((nt ? ema_kernel<scalar_t, true> : ema_kernel<scalar_t, false>),
+                       dim3(tb.nblocks), dim3(kThreads), 0, stream(), tb.ents(), tb.blks(),
+                       (float)beta, sp, cp, start);
   });
   IAMD_LAUNCH_CHECK();
 }
@@ -947,8 +826,7 @@ void mt_scale(const std::vector<at::Tensor>& xs, const at::Tensor& s) {
   auto sf = s.to(at::kFloat).contiguous();
   IAMD_DISPATCH_FLOAT_TYPES(dt, "mt_scale", [&] {
     hipLaunchKernelGGL((scale_kernel<scalar_t>), dim3(tb.nblocks), dim3(kThreads), 0, stream(),
-                       reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr()),
-                       tb.blocks.data_ptr<int>(), sf.data_ptr<float>());
+                       tb.ents(), tb.blks(), sf.data_ptr<float>());
   });
   IAMD_LAUNCH_CHECK();
 }
@@ -962,45 +840,15 @@ at::Tensor mt_sqnorm(const std::vector<at::Tensor>& xs) {
   auto part = at::empty({(int64_t)tb.nblocks}, xs[0].options().dtype(at::kFloat));
   IAMD_DISPATCH_FLOAT_TYPES(dt, "mt_sqnorm", [&] {
     hipLaunchKernelGGL((sqnorm_kernel<scalar_t>), dim3(tb.nblocks), dim3(kThreads), 0, stream(),
-                       reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr()),
-                       tb.blocks.data_ptr<int>(), part.data_ptr<float>());
+                       tb.ents(), tb.blks(), part.data_ptr<float>());
   });
-  hipLaunchKernelGGL(reduce_block_partials, dim3(1), dim3(kThreads), 0, stream(),
-                     part.data_ptr<float>(), tb.blocks.data_ptr<int>(), tb.nblocks, true,
-                     out.data_ptr<float>());
+  hipLaunchKernelGGL(reduce_block_partials<1>, dim3(1), dim3(kThreads), 0, stream(),
+                     part.data_ptr<float>(), tb.blks(), tb.nblocks, true, out.data_ptr<float>());
   IAMD_LAUNCH_CHECK();
   return out;
 }
 
 namespace {
-
-// The device learning rate of mt_fromage / mt_madam: hyper[0] (a replayed graph sees a changed
-// value); null = use the host argument.
-const float* lr_hyper(const c10::optional<at::Tensor>& hyper, const char* what) {
-  if (!hyper.has_value() || !hyper->defined()) return nullptr;
-  IAMD_CHECK(hyper->is_cuda() && hyper->scalar_type() == at::kFloat && hyper->numel() >= 1 &&
-                 hyper->is_contiguous(),
-             what, ": hyper must be a contiguous fp32 device tensor [lr, ...]");
-  return hyper->data_ptr<float>();
-}
-
-// Optional bf16 shadows, one per parameter (an empty tensor = none for that parameter); an empty
-// list = none at all, returned as a list of empty tensors so the table slots stay put.
-std::vector<at::Tensor> shadow_list(const std::vector<at::Tensor>& shadows,
-                                    const std::vector<at::Tensor>& params, const char* what) {
-  if (shadows.empty())
-    return std::vector<at::Tensor>(params.size(),
-                                   at::empty({0}, params[0].options().dtype(at::kBFloat16)));
-  IAMD_CHECK(shadows.size() == params.size(), what, ": shadow list size");
-  for (size_t i = 0; i < shadows.size(); ++i) {
-    if (shadows[i].numel() == 0) continue;
-    IAMD_CHECK(shadows[i].scalar_type() == at::kBFloat16 && shadows[i].is_cuda() &&
-                   shadows[i].sizes() == params[i].sizes() &&
-                   shadows[i].strides() == params[i].strides(),
-               what, ": a shadow must be a bf16 tensor laid out like its parameter");
-  }
-  return shadows;
-}
 
 void check_madam_states(const std::vector<at::Tensor>& states, size_t n, const char* what) {
   IAMD_CHECK(states.size() == n, what, ": state list size");
@@ -1020,29 +868,24 @@ void mt_fromage(const std::vector<at::Tensor>& params, const std::vector<at::Ten
   IAMD_CHECK(params.size() == grads.size(), "mt_fromage: list sizes differ");
   check_same_dtype(params, at::kFloat, "mt_fromage params");
   const auto gdt = grads[0].scalar_type();
-  IAMD_CHECK(gdt == at::kFloat || gdt == at::kBFloat16, "mt_fromage: grads must be fp32 or bf16");
   check_same_dtype(grads, gdt, "mt_fromage grads");
-  Table& tb = get_table({params, grads, shadow_list(shadows, params, "mt_fromage")},
-                        params[0].device());
-  if (tb.nblocks == 0) return;
-  const int T = (int)params.size();
-  auto ents = reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr());
-  auto blks = tb.blocks.data_ptr<int>();
-  // (both fully written by the kernels below: no memset node in a captured step)
-  auto part = at::empty({(int64_t)tb.nblocks, 2}, params[0].options());
-  auto norms = at::empty({(int64_t)T, 2}, params[0].options());
-#define IAMD_FROMAGE_LAUNCH(G)                                                                  \
-  do {                                                                                          \
-    hipLaunchKernelGGL((fromage_norm_kernel<G>), dim3(tb.nblocks), dim3(kThreads), 0, stream(), \
-                       ents, blks, part.data_ptr<float>());                                     \
-    hipLaunchKernelGGL(reduce_block_partials2, dim3(T), dim3(kThreads), 0, stream(),            \
-                       part.data_ptr<float>(), blks, tb.nblocks, norms.data_ptr<float>());      \
-    hipLaunchKernelGGL((fromage_kernel<G>), dim3(tb.nblocks), dim3(kThreads), 0, stream(), ents, \
-                       blks, norms.data_ptr<float>(), (float)lr, hp);                           \
-  } while (0)
-  if (gdt == at::kFloat) IAMD_FROMAGE_LAUNCH(float);
-  else IAMD_FROMAGE_LAUNCH(__hip_bfloat16);
-#undef IAMD_FROMAGE_LAUNCH
+  dispatch_grad(gdt, "mt_fromage", [&](auto tag) {
+    using G = std::remove_pointer_t<decltype(tag)>;
+    Table& tb = get_table({params, grads, shadow_list(shadows, params, "mt_fromage")},
+                          params[0].device());
+    if (tb.nblocks == 0) return;
+    const int T = (int)params.size();
+    // (both fully written by the kernels below: no memset node in a captured step)
+    auto part = at::empty({(int64_t)tb.nblocks, 2}, params[0].options());
+    auto norms = at::empty({(int64_t)T, 2}, params[0].options());
+    hipLaunchKernelGGL((fromage_norm_kernel<G>), dim3(tb.nblocks), dim3(kThreads), 0, stream(),
+                       tb.ents(), tb.blks(), part.data_ptr<float>());
+    hipLaunchKernelGGL(reduce_block_partials<2>, dim3(T), dim3(kThreads), 0, stream(),
+                       part.data_ptr<float>(), tb.blks(), tb.nblocks, false,
+                       norms.data_ptr<float>());
+    hipLaunchKernelGGL((fromage_kernel<G>), dim3(tb.nblocks), dim3(kThreads), 0, stream(),
+                       tb.ents(), tb.blks(), norms.data_ptr<float>(), (float)lr, hp);
+  });
   IAMD_LAUNCH_CHECK();
 }
 
@@ -1055,17 +898,16 @@ void mt_madam_init(const std::vector<at::Tensor>& params, const std::vector<at::
   check_madam_states(states, params.size(), "mt_madam_init");
   Table& tb = get_table({params, states}, params[0].device());
   const int T = (int)params.size();
-  auto ents = reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr());
   auto sums = at::empty({(int64_t)T}, params[0].options());
   auto part = at::empty({(int64_t)std::max(tb.nblocks, 1)}, params[0].options());
   if (tb.nblocks)
-    hipLaunchKernelGGL((sqnorm_kernel<float>), dim3(tb.nblocks), dim3(kThreads), 0, stream(), ents,
-                       tb.blocks.data_ptr<int>(), part.data_ptr<float>());
-  hipLaunchKernelGGL(reduce_block_partials, dim3(T), dim3(kThreads), 0, stream(),
-                     part.data_ptr<float>(), tb.blocks.data_ptr<int>(), tb.nblocks, false,
+    hipLaunchKernelGGL((sqnorm_kernel<float>), dim3(tb.nblocks), dim3(kThreads), 0, stream(),
+                       tb.ents(), tb.blks(), part.data_ptr<float>());
+  hipLaunchKernelGGL(reduce_block_partials<1>, dim3(T), dim3(kThreads), 0, stream(),
+                     part.data_ptr<float>(), tb.blks(), tb.nblocks, false,
                      sums.data_ptr<float>());
   hipLaunchKernelGGL(madam_max_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0,
-                     stream(), ents, T, sums.data_ptr<float>(), (float)scale);
+                     stream(), tb.ents(), T, sums.data_ptr<float>(), (float)scale);
   IAMD_LAUNCH_CHECK();
 }
 
@@ -1080,25 +922,21 @@ void mt_madam(const std::vector<at::Tensor>& params, const std::vector<at::Tenso
   check_same_dtype(params, at::kFloat, "mt_madam params");
   check_same_dtype(exp_avg_sqs, at::kFloat, "mt_madam exp_avg_sq");
   const auto gdt = grads[0].scalar_type();
-  IAMD_CHECK(gdt == at::kFloat || gdt == at::kBFloat16, "mt_madam: grads must be fp32 or bf16");
   check_same_dtype(grads, gdt, "mt_madam grads");
   check_madam_states(states, params.size(), "mt_madam");
   IAMD_CHECK(!g_bound.has_value() || *g_bound >= 0.0, "mt_madam: g_bound must be >= 0 or None");
-  Table& tb = get_table({params, grads, exp_avg_sqs, shadow_list(shadows, params, "mt_madam"),
-                         states}, params[0].device());
-  const int T = (int)params.size();
-  auto ents = reinterpret_cast<const TensorEntry*>(tb.entries.data_ptr());
-  hipLaunchKernelGGL(madam_step_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0,
-                     stream(), ents, T);
   const float bound = g_bound.has_value() ? (float)*g_bound : -1.f;
-  if (tb.nblocks) {
-    if (gdt == at::kFloat)
-      hipLaunchKernelGGL((madam_kernel<float>), dim3(tb.nblocks), dim3(kThreads), 0, stream(),
-                         ents, tb.blocks.data_ptr<int>(), (float)lr, bound, hp);
-    else
-      hipLaunchKernelGGL((madam_kernel<__hip_bfloat16>), dim3(tb.nblocks), dim3(kThreads), 0,
-                         stream(), ents, tb.blocks.data_ptr<int>(), (float)lr, bound, hp);
-  }
+  dispatch_grad(gdt, "mt_madam", [&](auto tag) {
+    using G = std::remove_pointer_t<decltype(tag)>;
+    Table& tb = get_table({params, grads, exp_avg_sqs, shadow_list(shadows, params, "mt_madam"),
+                           states}, params[0].device());
+    const int T = (int)params.size();
+    hipLaunchKernelGGL(madam_step_kernel, dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                       stream(), tb.ents(), T);
+    if (tb.nblocks)
+      hipLaunchKernelGGL((madam_kernel<G>), dim3(tb.nblocks), dim3(kThreads), 0, stream(),
+                         tb.ents(), tb.blks(), (float)lr, bound, hp);
+  });
   IAMD_LAUNCH_CHECK();
 }
 

@@ -55,7 +55,8 @@ __device__ __forceinline__ int64_t logical_col(const SnEntry& e, int64_t c) {
   return (int64_t)(cc - q * cin) * e.cl_khw + q;
 }
 
-__device__ float block_sum(float v, float* sh) {
+// (the sum in every thread, unlike common.h's block_sum)
+__device__ float block_sum_all(float v, float* sh) {
   v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -166,7 +167,7 @@ __global__ void __launch_bounds__(kT) sn_tnorm(const SnEntry* __restrict__ ents,
   const SnEntry e = ents[blockIdx.x];
   float acc = 0.f;
   for (int64_t c = threadIdx.x; c < e.w; c += kT) acc = fmaf(e.t[c], e.t[c], acc);
-  acc = block_sum(acc, sh);
+  acc = block_sum_all(acc, sh);
   if (threadIdx.x == 0) scal[4 * blockIdx.x] = acc;
 }
 
@@ -254,7 +255,7 @@ __global__ void __launch_bounds__(kT) sn_final(const SnEntry* __restrict__ ents,
   if (update) {
     float acc = 0.f;
     for (int64_t r = threadIdx.x; r < e.h; r += kT) acc = fmaf(e.s[r], e.s[r], acc);
-    const float ss = block_sum(acc, sh);
+    const float ss = block_sum_all(acc, sh);
     const float inv_s = 1.f / fmaxf(sqrtf(ss), eps);
     const float inv_t = 1.f / fmaxf(sqrtf(scal[4 * blockIdx.x]), eps);
     for (int64_t r = threadIdx.x; r < e.h; r += kT) e.u[r] = e.s[r] * inv_s;
@@ -266,7 +267,7 @@ __global__ void __launch_bounds__(kT) sn_final(const SnEntry* __restrict__ ents,
   } else {
     float acc = 0.f;
     for (int64_t r = threadIdx.x; r < e.h; r += kT) acc = fmaf(e.u[r], e.s[r], acc);
-    const float d = block_sum(acc, sh);
+    const float d = block_sum_all(acc, sh);
     if (threadIdx.x == 0) sigma[blockIdx.x] = d;
   }
 }
@@ -649,15 +650,9 @@ snb_reduce(const G* __restrict__ g, const WT* __restrict__ W, int64_t n,
   } else {
     for (int64_t i = gtid; i < n; i += gsz) acc = fmaf(to_f<G>(g[i]), to_f<WT>(W[i]), acc);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int k = 0; k < kSnbT / 64; ++k) s += sh[k];
-    // a bf16 W read is the shadow bf16(W), already the weight itself: no rescale needed
-    partial[blockIdx.x] = s;
-  }
+  // a bf16 W read is the shadow bf16(W), already the weight itself: no rescale needed
+  const float s = block_sum<kSnbT>(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 template <typename G>
