@@ -98,6 +98,62 @@ bias_act_bwd_cl(const T* __restrict__ out, const T* __restrict__ dy, T* __restri
   }
 }
 
+// bias_act_bwd_cl (with the activation) for NG output tensors of one shape in ONE launch,
+// blockIdx.z = group: group g's dx goes to channels [g * C, (g + 1) * C) of one [rows][ldx]
+// buffer (the channel-concatenated dy of a grouped weight gradient, conv_wgrad_mfma.hip) and
+// its partial sums to the same columns of partial [P][ldx]. Per element and per column the same
+// operations in the same order as the kernel above on that group alone. The tensor table
+// travels by value in the launch arguments.
+constexpr int kMaxActGroups = 8;
+struct ActGroupTab {
+  const void* out[kMaxActGroups];
+  const void* dy[kMaxActGroups];
+};
+
+template <typename T, int VEC>
+__global__ void __launch_bounds__(kThreads)
+bias_act_bwd_cl_grouped(ActGroupTab t, T* __restrict__ dx, int64_t rows, int C, int ldx,
+                        int64_t rows_per_block, int tpr, float slope,
+                        float* __restrict__ partial) {
+  __shared__ float sh[kThreads][VEC];
+  const int grp = blockIdx.z;
+  const T* __restrict__ out = static_cast<const T*>(t.out[grp]);
+  const T* __restrict__ dy = static_cast<const T*>(t.dy[grp]);
+  const int tid = threadIdx.x;
+  const int rpb = kThreads / tpr;
+  const int tc = tid % tpr, r = tid / tpr;
+  const int c0 = (blockIdx.y * tpr + tc) * VEC;
+  const bool active = r < rpb && c0 < C;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = min(rows, r0 + rows_per_block);
+  float acc[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+  if (active) {
+    for (int64_t row = r0 + r; row < r1; row += rpb) {
+      float o[VEC], g[VEC];
+      load_vec<T, VEC>(dy + row * C + c0, g);
+      load_vec<T, VEC>(out + row * C + c0, o);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) g[k] *= act_grad(o[k], slope);
+      store_vec<T, VEC>(dx + row * ldx + grp * C + c0, g);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) acc[k] += g[k];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) sh[tid][k] = acc[k];
+  __syncthreads();
+  if (active && r == 0) {
+    for (int rr = 1; rr < rpb; ++rr)
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) acc[k] += sh[tid + rr * tpr][k];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k)
+      if (c0 + k < C) partial[(int64_t)blockIdx.x * ldx + grp * C + c0 + k] = acc[k];
+  }
+}
+
 template <typename T, int VEC>
 __global__ void __launch_bounds__(kThreads)
 bias_act_bwd_nchw(const T* __restrict__ out, const T* __restrict__ dy, T* __restrict__ dx, int N,
@@ -328,6 +384,57 @@ std::vector<at::Tensor> bias_act_bwd(const at::Tensor& out, const at::Tensor& dy
   auto db = buf.narrow(0, (int64_t)P * C, C);
   hipLaunchKernelGGL(col_sum, dim3(ceil_div(C, 64)), dim3(64, kColRows), 0, stream(),
                      partial.data_ptr<float>(), P, C, db.data_ptr<float>());
+  IAMD_LAUNCH_CHECK();
+  return {dx, db};
+}
+
+// bias_act_bwd of n channels-last outputs of one shape [N, C, H, W] (C % 8 == 0, slope != 1) in
+// one launch plus one column sum: returns (dx [N, n * C, H, W] channels-last — group g's
+// activation gradient in channels g * C .. — and dbias [n * C] fp32). Each group's numbers are
+// those of bias_act_bwd(outs[g], dys[g], slope).
+std::vector<at::Tensor> bias_act_bwd_grouped(const std::vector<at::Tensor>& outs,
+                                             const std::vector<at::Tensor>& dys, double slope) {
+  const int n = (int)outs.size();
+  IAMD_CHECK(n >= 1 && n <= kMaxActGroups && (int)dys.size() == n,
+             "bias_act_bwd_grouped: 1..", kMaxActGroups, " outputs, one dy each");
+  IAMD_CHECK(slope != 1.0, "bias_act_bwd_grouped: an activation expected");
+  const at::Tensor& o0 = outs[0];
+  const int N = (int)o0.size(0), C = (int)o0.size(1);
+  ActGroupTab t;
+  for (int g = 0; g < kMaxActGroups; ++g) t.out[g] = t.dy[g] = nullptr;
+  for (int g = 0; g < n; ++g) {
+    IAMD_CHECK(outs[g].is_cuda() && is_cl(outs[g]) && outs[g].sizes() == o0.sizes() &&
+                   outs[g].scalar_type() == o0.scalar_type() && dys[g].is_cuda() &&
+                   dys[g].sizes() == o0.sizes() && dys[g].scalar_type() == o0.scalar_type() &&
+                   dys[g].is_contiguous(at::MemoryFormat::ChannelsLast),
+               "bias_act_bwd_grouped: packed channels-last tensors of one shape and dtype");
+    t.out[g] = outs[g].data_ptr();
+    t.dy[g] = dys[g].data_ptr();
+  }
+  IAMD_CHECK(C % 8 == 0, "bias_act_bwd_grouped: channels must be a multiple of 8");
+  const BwdPlan plan = bwd_plan(o0, slope);
+  IAMD_CHECK(plan.chan_fast && (plan.vec == 8 || plan.vec == 4),
+             "bias_act_bwd_grouped: 2- or 4-byte elements expected");
+  const int P = plan.P, ldx = n * C;
+  auto dx = at::empty({N, (int64_t)ldx, o0.size(2), o0.size(3)},
+                      o0.options().memory_format(at::MemoryFormat::ChannelsLast));
+  at::Tensor buf = at::empty({(int64_t)P * ldx + ldx}, o0.options().dtype(at::kFloat));
+  at::Tensor partial = buf.narrow(0, 0, (int64_t)P * ldx);
+  IAMD_DISPATCH_FLOAT_TYPES(o0.scalar_type(), "bias_act_bwd_grouped", [&] {
+    auto dp = reinterpret_cast<scalar_t*>(dx.data_ptr());
+    auto launch = [&](auto vt) {
+      constexpr int V = decltype(vt)::value;
+      hipLaunchKernelGGL((bias_act_bwd_cl_grouped<scalar_t, V>), dim3(P, plan.nzc, n),
+                         dim3(kThreads), 0, stream(), t, dp, plan.rows, C, ldx,
+                         plan.rows_per_block, plan.tpr, (float)slope, partial.data_ptr<float>());
+    };
+    if (plan.vec == 8) launch(std::integral_constant<int, 8>());
+    else launch(std::integral_constant<int, 4>());
+  });
+  IAMD_LAUNCH_CHECK();
+  auto db = buf.narrow(0, (int64_t)P * ldx, ldx);
+  hipLaunchKernelGGL(col_sum, dim3(ceil_div(ldx, 64)), dim3(64, kColRows), 0, stream(),
+                     partial.data_ptr<float>(), P, ldx, db.data_ptr<float>());
   IAMD_LAUNCH_CHECK();
   return {dx, db};
 }

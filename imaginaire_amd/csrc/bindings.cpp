@@ -141,6 +141,16 @@ at::Tensor conv2d_mfma(const at::Tensor& x, const at::Tensor& w, const c10::opti
                        double slope, int64_t nb, int64_t ncv,
                        const c10::optional<at::Tensor>& residual,
                        const c10::optional<at::Tensor>& ascale, int64_t pad_mode);
+std::vector<at::Tensor> conv2d_mfma_grouped(const at::Tensor& x, const std::vector<at::Tensor>& ws,
+                                            const std::vector<at::Tensor>& biases,
+                                            const std::vector<at::Tensor>& ascales, int64_t ph,
+                                            int64_t pw, double slope);
+std::vector<at::Tensor> conv2d_wgrad_mfma_grouped(
+    const at::Tensor& dy, const at::Tensor& x, int64_t n, int64_t KH, int64_t KW, int64_t ph,
+    int64_t pw, int64_t out_cin, int64_t variant, const std::vector<std::vector<at::Tensor>>& sns,
+    const std::vector<c10::optional<at::Tensor>>& dsts);
+std::vector<at::Tensor> bias_act_bwd_grouped(const std::vector<at::Tensor>& outs,
+                                             const std::vector<at::Tensor>& dys, double slope);
 at::Tensor conv2d_dgrad_mfma(const at::Tensor& dy, const at::Tensor& w, int64_t ph, int64_t pw,
                              int64_t ncv, const c10::optional<at::Tensor>& ascale);
 at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t KH, int64_t KW,
@@ -243,6 +253,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pw"), py::arg("dh"), py::arg("dw"), py::arg("slope"), py::arg("nb") = 1,
         py::arg("ncv") = -1, py::arg("residual") = py::none(), py::arg("ascale") = py::none(),
         py::arg("pad_mode") = 0);
+  m.def("conv2d_mfma_grouped", &iamd::conv2d_mfma_grouped,
+        "G stride-1 convs of one input in one k10 v4 launch (one output per group; an empty "
+        "list: not grouped, nothing launched)",
+        py::arg("x"), py::arg("ws"), py::arg("biases"), py::arg("ascales"), py::arg("ph"),
+        py::arg("pw"), py::arg("slope"));
+  m.def("conv2d_wgrad_mfma_grouped", &iamd::conv2d_wgrad_mfma_grouped,
+        "weight gradients of n convs of one input from their channel-concatenated dy: one k11 "
+        "launch, one finalize pass (per-group spectral-norm backward and destination)",
+        py::arg("dy"), py::arg("x"), py::arg("n"), py::arg("KH"), py::arg("KW"), py::arg("ph"),
+        py::arg("pw"), py::arg("out_cin"), py::arg("variant"), py::arg("sns"), py::arg("dsts"));
+  m.def("bias_act_bwd_grouped", &iamd::bias_act_bwd_grouped,
+        "k2 backward of n outputs of one shape: dx channel-concatenated, dbias [n * C]",
+        py::arg("outs"), py::arg("dys"), py::arg("slope"));
   m.def("conv2d_dgrad_mfma", &iamd::conv2d_dgrad_mfma,
         "stride-1 conv data gradient from the forward weight (k10 v4 transposed-weight path)",
         py::arg("dy"), py::arg("w"), py::arg("ph"), py::arg("pw"), py::arg("ncv") = -1,

@@ -194,6 +194,136 @@ wgrad_finalize_sn_kernel(const float* __restrict__ part, float* __restrict__ out
   }
 }
 
+// ---- grouped finalize: the weight gradients of NG convs that share their input -------------
+//
+// One k11 launch over the channel-concatenated dy of the group wrote slabs [S][NG * Cpg][KK]
+// [Cip] (group g: rows g * Cpg ..). blockIdx.y = group: the pass of wgrad_finalize_kernel /
+// wgrad_finalize_sn_kernel (fp32 out) over that group's rows, into its own destination, with its
+// own u, v, sigma and its own <G, W>. The sums run in the order the layer's own launch and
+// finalize would use (same G, same slab order), and with SN the group's <G, W> partials are
+// summed in the order sn_coef sums the layer's own: a k11 launch of the same kernel and S then
+// gives the same bits grouped or not. The table travels by value in the launch arguments.
+constexpr int kMaxWgradGroups = 8;
+struct WgradGroupTab {
+  float* out[kMaxWgradGroups];
+  const float* u[kMaxWgradGroups];
+  const float* v[kMaxWgradGroups];
+  const float* sigma[kMaxWgradGroups];
+  // grid of the k11 launch that wrote dotp[blockIdx.x] (its decode, conv_wgrad_mfma.hip: bid =
+  // xcd_remap(blockIdx.x), split-major, then (tap or filter row, n-tile, c-tile)): gx blocks, T
+  // taps / filter rows, nNt n-tiles (nNtg per group), nCt c-tiles
+  int gx, T, nNt, nNtg, nCt;
+};
+
+// inverse of xcd_remap (common.h): the block id whose remapped id is bid
+__device__ __forceinline__ int xcd_unmap(int bid, int nwg) {
+  constexpr int kXcd = 8;
+  if (nwg <= kXcd) return bid;
+  const int q = nwg / kXcd, r = nwg % kXcd;
+  int xcd, local;
+  if (bid < r * (q + 1)) {
+    xcd = bid / (q + 1);
+    local = bid - xcd * (q + 1);
+  } else {
+    const int t = bid - r * (q + 1);
+    xcd = r + t / q;
+    local = t - (t / q) * q;
+  }
+  return local * kXcd + xcd;
+}
+
+// where the grouped launch left the <G, W> partial that the layer's own launch (the same kernel
+// and splits, nNtg n-tiles) would have written to dotp[k]
+__device__ __forceinline__ int group_dot_index(const WgradGroupTab& t, int g, int k) {
+  const int per_l = t.nNtg * t.nCt, per_g = t.nNt * t.nCt;
+  const int tiles_l = t.T * per_l, tiles_g = t.T * per_g;
+  const int S = t.gx / tiles_g;
+  const int bid = xcd_remap(k, tiles_l * S);
+  const int split = bid / tiles_l, tile = bid - split * tiles_l;
+  const int tt = tile / per_l, r2 = tile - tt * per_l;
+  const int nt = r2 / t.nCt, ct = r2 - nt * t.nCt;
+  return xcd_unmap(split * tiles_g + tt * per_g + (g * t.nNtg + nt) * t.nCt + ct, t.gx);
+}
+
+template <bool VEC, bool SN>
+__global__ void __launch_bounds__(kT)
+wgrad_finalize_grouped_kernel(const float* __restrict__ part, WgradGroupTab t, int S, int Cop,
+                              int Cpg, int Cip, int Cout, int Cin, int KK, int G,
+                              const float* __restrict__ dotp) {
+  __shared__ float4 red[kT];
+  __shared__ float dsh[kT / 64];
+  const int grp = blockIdx.y;
+  const int opb = kT / G;
+  const int tid = threadIdx.x, o = tid % opb, g = tid / opb;
+  float inv = 1.f, cf = 0.f;  // 1 / sigma, <G, W> / sigma^2 (as sn_coef)
+  if constexpr (SN) {
+    const int ndot = t.gx / t.nNt * t.nNtg;
+    float dd = 0.f;
+    for (int k = tid; k < ndot; k += kT) dd += dotp[group_dot_index(t, grp, k)];
+    dd = wave_sum(dd);
+    if ((tid & 63) == 0) dsh[tid >> 6] = dd;
+    __syncthreads();
+    float dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < kT / 64; ++k) dot += dsh[k];
+    inv = 1.f / t.sigma[grp][0];
+    cf = dot * inv * inv;
+  }
+  const float* __restrict__ pg = part + (int64_t)grp * Cpg * KK * Cip;
+  float* __restrict__ out = t.out[grp];
+  const float* __restrict__ u = t.u[grp];
+  const float* __restrict__ v = t.v[grp];
+  const int per = VEC ? Cin / 4 : Cin;
+  const int64_t n = (int64_t)Cout * KK * per;
+  const int64_t slab = (int64_t)Cop * KK * Cip;
+  for (int64_t i0 = (int64_t)blockIdx.x * opb; i0 < n; i0 += (int64_t)gridDim.x * opb) {
+    const int64_t i = i0 + o;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int64_t rt = 0, src = 0;
+    int c = 0, tp = 0, co = 0;
+    if (i < n) {
+      c = (int)(i % per);
+      rt = i / per;  // co * KK + t
+      tp = (int)(rt % KK);
+      co = (int)(rt / KK);
+      src = ((int64_t)co * KK + tp) * Cip + (VEC ? c * 4 : c);
+      for (int sl = g; sl < S; sl += G) {
+        if constexpr (VEC) {
+          const float4 w4 = *reinterpret_cast<const float4*>(pg + sl * slab + src);
+          acc.x += w4.x; acc.y += w4.y; acc.z += w4.z; acc.w += w4.w;
+        } else {
+          acc.x += pg[sl * slab + src];
+        }
+      }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    if (g == 0 && i < n) {
+      for (int k = 1; k < G; ++k) {
+        const float4 w4 = red[k * opb + o];
+        acc.x += w4.x; acc.y += w4.y; acc.z += w4.z; acc.w += w4.w;
+      }
+      if constexpr (SN) {
+        const float cu = cf * u[co];
+        if constexpr (VEC) {
+          const float* vv = v + (int64_t)c * 4 * KK + tp;
+          *reinterpret_cast<float4*>(out + rt * Cin + c * 4) =
+              make_float4(fmaf(acc.x, inv, -cu * vv[0]), fmaf(acc.y, inv, -cu * vv[KK]),
+                          fmaf(acc.z, inv, -cu * vv[2 * KK]), fmaf(acc.w, inv, -cu * vv[3 * KK]));
+        } else {
+          out[rt * Cin + c] = fmaf(acc.x, inv, -cu * v[(int64_t)c * KK + tp]);
+        }
+      } else if constexpr (VEC) {
+        float* dst = out + rt * Cin + c * 4;
+        dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z; dst[3] = acc.w;
+      } else {
+        out[rt * Cin + c] = acc.x;
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // padded index o -> source index along one axis (mode 0 reflect, 1 replicate)
 __device__ __forceinline__ int pad_src(int o, int p, int n, int mode) {
   int i = o - p;
@@ -819,6 +949,77 @@ at::Tensor wgrad_finalize_sn(const at::Tensor& part, int64_t S, int64_t Cop, int
                        u.data_ptr<float>(), v.data_ptr<float>(), sigma.data_ptr<float>());
   IAMD_LAUNCH_CHECK();
   return out;
+}
+
+// The finalize pass of a grouped weight gradient (wgrad_finalize_grouped_kernel): slabs
+// [S][ng * Cpg][KK][Cip] -> ng fp32 gradients [Cout, Cin, KH, KW] (channels-last), each into
+// dsts[g] when given. sn[g] = {u, v, sigma} (with dotp: the <G, W> partials of the k11 launch
+// whose grid is (gx, T, nNt, nCt)), or sn empty: plain sums.
+std::vector<at::Tensor> wgrad_finalize_grouped(
+    const at::Tensor& part, int64_t S, int64_t ng, int64_t Cpg, int64_t Cip, int64_t Cout,
+    int64_t Cin, int64_t KH, int64_t KW, const std::vector<std::vector<at::Tensor>>& sn,
+    const at::Tensor& dotp, int64_t gx, int64_t T, int64_t nNt, int64_t nCt,
+    const std::vector<c10::optional<at::Tensor>>& dsts) {
+  const int64_t Cop = ng * Cpg;
+  IAMD_CHECK(ng >= 1 && ng <= kMaxWgradGroups, "wgrad_finalize_grouped: 1..", kMaxWgradGroups,
+             " groups");
+  IAMD_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat && part.is_contiguous() &&
+                 part.numel() >= S * Cop * KH * KW * Cip && Cout <= Cpg && Cin <= Cip,
+             "wgrad_finalize_grouped: slab shape");
+  const bool use_sn = !sn.empty();
+  IAMD_CHECK(!use_sn || ((int64_t)sn.size() == ng && dotp.defined() &&
+                         dotp.scalar_type() == at::kFloat && dotp.is_contiguous() &&
+                         nNt % ng == 0 && gx % (T * nNt * nCt) == 0 && dotp.numel() == gx),
+             "wgrad_finalize_grouped: one {u, v, sigma} per group and the k11 grid of the "
+             "partials");
+  WgradGroupTab t;
+  t.gx = (int)gx; t.T = (int)T; t.nNt = (int)nNt; t.nNtg = (int)(nNt / ng); t.nCt = (int)nCt;
+  std::vector<at::Tensor> outs, keep;
+  for (int g = 0; g < kMaxWgradGroups; ++g) {
+    t.out[g] = nullptr; t.u[g] = nullptr; t.v[g] = nullptr; t.sigma[g] = nullptr;
+  }
+  for (int g = 0; g < (int)ng; ++g) {
+    outs.push_back(finalize_out(part, Cout, Cin, KH, KW, at::kFloat,
+                                g < (int)dsts.size() ? dsts[g] : c10::nullopt));
+    t.out[g] = outs.back().data_ptr<float>();
+    if (use_sn) {
+      IAMD_CHECK(sn[g].size() == 3, "wgrad_finalize_grouped: sn[g] = {u, v, sigma}");
+      const at::Tensor u = sn[g][0].contiguous(), v = sn[g][1].contiguous();
+      const at::Tensor& sigma = sn[g][2];
+      IAMD_CHECK(u.is_cuda() && v.is_cuda() && sigma.is_cuda() &&
+                     u.scalar_type() == at::kFloat && v.scalar_type() == at::kFloat &&
+                     sigma.scalar_type() == at::kFloat && u.numel() == Cout &&
+                     v.numel() == Cin * KH * KW && sigma.numel() == 1,
+                 "wgrad_finalize_grouped: u / v / sigma");
+      keep.push_back(u);
+      keep.push_back(v);
+      t.u[g] = u.data_ptr<float>();
+      t.v[g] = v.data_ptr<float>();
+      t.sigma[g] = sigma.data_ptr<float>();
+    }
+  }
+  const int KK = (int)(KH * KW);
+  const bool vec = Cin % 4 == 0 && Cip % 4 == 0;
+  const int64_t n = Cout * KK * (vec ? Cin / 4 : Cin);
+  if (n == 0) return outs;
+  int G = 1;  // (wgrad_finalize's rule on one group's outputs: the same sum order)
+  while (G < 16 && G < S && (n * G * 2 <= (int64_t)256 * 4096 || G * 8 < S)) G *= 2;
+  const int opb = kT / G;
+  const int blocks = (int)std::min<int64_t>((n + opb - 1) / opb, 8192);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(blocks, (unsigned)ng), dim3(kT), 0, stream(),
+                       part.data_ptr<float>(), t, (int)S, (int)Cop, (int)Cpg, (int)Cip, (int)Cout,
+                       (int)Cin, KK, G, use_sn ? dotp.data_ptr<float>() : nullptr);
+  };
+  if (use_sn) {
+    if (vec) launch(wgrad_finalize_grouped_kernel<true, true>);
+    else launch(wgrad_finalize_grouped_kernel<false, true>);
+  } else {
+    if (vec) launch(wgrad_finalize_grouped_kernel<true, false>);
+    else launch(wgrad_finalize_grouped_kernel<false, false>);
+  }
+  IAMD_LAUNCH_CHECK();
+  return outs;
 }
 
 namespace {

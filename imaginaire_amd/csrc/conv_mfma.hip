@@ -773,8 +773,10 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v3(ConvArgs a) {
 // pad_map'ed once into a_off (no column is out of the image) and the filter row of each outer
 // step is mapped per lane from the segment's ih0, which a_km then holds instead of the
 // row-validity mask (a_off = kOobOffset marks the rows past the last segment).
+// The body is the tile (mt, nt) of split blockIdx.y: the kernel below runs it for one conv, the
+// grouped kernel after it for the conv its n-tile belongs to.
 template <int KW, bool HAS_BIAS, bool BT, bool PF, bool PM = false>
-__global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4(ConvArgs a) {
+__device__ __forceinline__ void conv_v4_impl(const ConvArgs& a, int mt, int nt) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int BM = 256, BN = 128;
   constexpr int kArows = 320;                     // window rows per buffer: 5 DMA rounds of 64
@@ -786,8 +788,6 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4(ConvArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int mt = bid / a.nNt, nt = bid - mt * a.nNt;
   const int m0 = mt * BM, n0 = nt * BN;
   const int HoWo = a.Ho * a.Wo;
   const int SW = a.Wo >= BM ? BM : a.Wo;          // pixels per output-row segment
@@ -1086,6 +1086,81 @@ __global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4(ConvArgs a) {
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
+template <int KW, bool HAS_BIAS, bool BT, bool PF, bool PM = false>
+__global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4(ConvArgs a) {
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int mt = bid / a.nNt;
+  conv_v4_impl<KW, HAS_BIAS, BT, PF, PM>(a, mt, bid - mt * a.nNt);
+}
+
+// ---- grouped v4: G convs of ONE input with G weights of equal shape, one launch ------------
+//
+// The first conv of every SPADE norm's label MLP at one resolution reads the same resized label
+// map; each alone has Cout = 128, one n-tile, and a grid that fills 3-50% of the chip below
+// 128 x 256. Here the grid's n-tile index runs over all groups' n-tiles (a.nNt = G * npg) and
+// selects the conv: its weight rows, bias, sigma and its own dense NHWC output come from the
+// table, which travels by value in the launch arguments (no device table, no copy, no memset
+// node in a captured graph). The tile itself is conv_v4_impl on the selected conv's ConvArgs,
+// so with the same split a group's output equals the conv run alone bit for bit. Split-K
+// slabs: group g's S slabs [S][M][Cout] start at part + g * pstride.
+constexpr int kMaxConvGroups = 8;
+struct ConvGroupTab {
+  const __hip_bfloat16* w[kMaxConvGroups];
+  const float* bias[kMaxConvGroups];
+  const float* ascale[kMaxConvGroups];
+  __hip_bfloat16* y[kMaxConvGroups];
+  int npg;          // 128-channel n-tiles per group
+  int64_t pstride;  // floats between two groups' split-K slabs
+};
+
+template <int KW, bool HAS_BIAS>
+__global__ __launch_bounds__(512, 1) void conv_fwd_mfma_v4_grouped(ConvArgs a, ConvGroupTab t) {
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int mt = bid / a.nNt, ntt = bid - mt * a.nNt;
+  const int g = ntt / t.npg;
+  ConvArgs b = a;
+  b.w = t.w[g];
+  b.bias = t.bias[g];
+  b.ascale = t.ascale[g];
+  b.y = t.y[g];
+  if (a.part) b.part = a.part + (size_t)g * t.pstride;
+  conv_v4_impl<KW, HAS_BIAS, false, true, false>(b, mt, ntt - g * t.npg);
+}
+
+// conv_splitk_reduce for the grouped launch (blockIdx.y = group): the same sum, scale, bias
+// and activation per element, each group with its own slabs, bias, sigma and output.
+__global__ void __launch_bounds__(256)
+conv_splitk_reduce_grouped(const float* __restrict__ part, ConvGroupTab t, int S, int64_t MC,
+                           int C, float slope) {
+  const int g = blockIdx.y;
+  const float* __restrict__ pg = part + (size_t)g * t.pstride;
+  const float* __restrict__ bias = t.bias[g];
+  __hip_bfloat16* __restrict__ y = t.y[g];
+  const float asc = t.ascale[g] ? 1.f / t.ascale[g][0] : 1.f;
+  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < MC / 8;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = v * 8;
+    float acc[8];
+    const float4* p = reinterpret_cast<const float4*>(pg + e);
+    float4 lo = p[0], hi = p[1];
+    acc[0] = lo.x; acc[1] = lo.y; acc[2] = lo.z; acc[3] = lo.w;
+    acc[4] = hi.x; acc[5] = hi.y; acc[6] = hi.z; acc[7] = hi.w;
+    for (int s = 1; s < S; ++s) {
+      const float4* q = reinterpret_cast<const float4*>(pg + (int64_t)s * MC + e);
+      lo = q[0]; hi = q[1];
+      acc[0] += lo.x; acc[1] += lo.y; acc[2] += lo.z; acc[3] += lo.w;
+      acc[4] += hi.x; acc[5] += hi.y; acc[6] += hi.z; acc[7] += hi.w;
+    }
+    const int c = (int)(e % C);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      float r = fmaf(acc[k], asc, bias ? bias[c + k] : 0.f);
+      acc[k] = r > 0.f ? r : r * slope;
+    }
+    store_vec<__hip_bfloat16, 8>(y + e, acc);
+  }
+}
+
 // ---- k10 v5: row-window implicit GEMM, 256 x 256 tile, 8 waves of 128 x 64 -----------------
 //
 // v4's 64 x 64 wave tile reads 512 LDS bytes per MFMA (A and B fragments) and, with the DMA
@@ -1370,17 +1445,23 @@ bool v4_eligible(const ConvArgs& a) {
          ((int64_t)a.Ho * a.Wo) % 256 == 0;
 }
 
-void run_v4(ConvArgs& a, const at::Tensor& x, bool bt) {
-  const int Cout = a.Cout, KW = a.KW;
-  a.nNt = Cout / 128;
-  const int64_t tiles4 = (int64_t)(a.M / 256) * a.nNt;
-  const int nout = a.nk / KW;  // (filter row, channel block) outer steps
+// v4's split-K over the nout (filter row, channel block) outer steps for a grid of tiles4
+// blocks: sets a.kps, returns the number of splits
+int v4_split(ConvArgs& a, int64_t tiles4, int nout) {
   int S4 = 1;
   if (tiles4 < 256 && nout >= 8) S4 = (int)std::min<int64_t>((256 + tiles4 - 1) / tiles4, nout / 4);
   if (const char* e = std::getenv("IMAGINAIRE_AMD_CONV_SPLITK")) S4 = std::max(1, std::atoi(e));
   S4 = std::max(1, std::min(S4, nout));
   a.kps = ceil_div(nout, S4);
-  S4 = ceil_div(nout, a.kps);
+  return ceil_div(nout, a.kps);
+}
+
+void run_v4(ConvArgs& a, const at::Tensor& x, bool bt) {
+  const int Cout = a.Cout, KW = a.KW;
+  a.nNt = Cout / 128;
+  const int64_t tiles4 = (int64_t)(a.M / 256) * a.nNt;
+  const int nout = a.nk / KW;  // (filter row, channel block) outer steps
+  const int S4 = v4_split(a, tiles4, nout);
   at::Tensor part4;
   a.part = nullptr;
   if (S4 > 1) {
@@ -1423,6 +1504,43 @@ void run_v4(ConvArgs& a, const at::Tensor& x, bool bt) {
     const int blocks = (int)std::min<int64_t>((MC / 8 + 255) / 256, 8192);
     hipLaunchKernelGGL(conv_splitk_reduce, dim3(blocks), dim3(256), 0, stream(), a.part, a.bias,
                        a.y, S4, MC, Cout, a.slope, a);
+  }
+  IAMD_LAUNCH_CHECK();
+}
+
+// The grouped v4 launch: `a` describes ONE member conv (a.Cout = its channels), t the ngroups
+// members; run_v4's split rule on the grouped tile count, one slab allocation and one reduce.
+void run_v4_grouped(ConvArgs& a, ConvGroupTab& t, int ngroups, const at::Tensor& x) {
+  const int Cout = a.Cout, KW = a.KW;
+  t.npg = Cout / 128;
+  a.nNt = t.npg * ngroups;
+  const int64_t tiles4 = (int64_t)(a.M / 256) * a.nNt;
+  const int nout = a.nk / KW;
+  const int S4 = v4_split(a, tiles4, nout);
+  const int64_t MC = (int64_t)a.M * Cout;
+  t.pstride = (int64_t)S4 * MC;
+  at::Tensor part4;
+  a.part = nullptr;
+  if (S4 > 1) {
+    part4 = at::empty({(int64_t)ngroups * t.pstride}, x.options().dtype(at::kFloat));
+    a.part = part4.data_ptr<float>();
+  }
+  const dim3 grid4((unsigned)tiles4, (unsigned)S4, 1);
+  auto launch = [&](auto kv) {
+    constexpr int K = decltype(kv)::value;
+    if (t.bias[0])
+      hipLaunchKernelGGL((conv_fwd_mfma_v4_grouped<K, true>), grid4, dim3(512), 0, stream(), a, t);
+    else
+      hipLaunchKernelGGL((conv_fwd_mfma_v4_grouped<K, false>), grid4, dim3(512), 0, stream(), a, t);
+  };
+  if (KW == 5) launch(std::integral_constant<int, 5>());
+  else if (KW == 4) launch(std::integral_constant<int, 4>());
+  else launch(std::integral_constant<int, 3>());
+  if (S4 > 1) {
+    IAMD_LAUNCH_CHECK();
+    const int blocks = (int)std::min<int64_t>((MC / 8 + 255) / 256, 8192);
+    hipLaunchKernelGGL(conv_splitk_reduce_grouped, dim3(blocks, ngroups), dim3(256), 0, stream(),
+                       a.part, t, S4, MC, Cout, a.slope);
   }
   IAMD_LAUNCH_CHECK();
 }
@@ -1764,6 +1882,86 @@ at::Tensor conv2d_mfma(const at::Tensor& x, const at::Tensor& w, const c10::opti
   a.pmode = (int)pad_mode;
   run_conv(a, x);
   return y;
+}
+
+// G stride-1 convs of the same input in one v4 launch: ys[g] = act(conv2d(x, ws[g]) / sigma_g +
+// bias_g), every ws[g] a channels-last bf16 [Cout, Cin, KH, KW] of the same shape with
+// Cout % 128 == 0. biases / ascales: empty, or one fp32 tensor per group (ascales: the 1-element
+// sigma of a spectrally normalised weight, as conv2d_mfma's ascale). Returns one dense NHWC
+// output per group — or NO tensors ("not grouped", nothing launched) when conv2d_mfma would not
+// run these convs on the prefetching v4 tile: the caller then runs them one by one.
+std::vector<at::Tensor> conv2d_mfma_grouped(const at::Tensor& x, const std::vector<at::Tensor>& ws,
+                                            const std::vector<at::Tensor>& biases,
+                                            const std::vector<at::Tensor>& ascales, int64_t ph,
+                                            int64_t pw, double slope) {
+  const int G = (int)ws.size();
+  IAMD_CHECK(G >= 1, "conv2d_mfma_grouped: no weights");
+  IAMD_CHECK(biases.empty() || (int)biases.size() == G, "conv2d_mfma_grouped: one bias per group");
+  IAMD_CHECK(ascales.empty() || (int)ascales.size() == G,
+             "conv2d_mfma_grouped: one ascale per group");
+  IAMD_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 4 &&
+                 x.is_contiguous(at::MemoryFormat::ChannelsLast),
+             "conv2d_mfma_grouped: x must be a packed channels-last bf16 CUDA tensor");
+  const int B = (int)x.size(0), Cin = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
+  const at::Tensor& w0 = ws[0];
+  for (const at::Tensor& w : ws)
+    IAMD_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 4 &&
+                   w.is_contiguous(at::MemoryFormat::ChannelsLast) && w.sizes() == w0.sizes() &&
+                   w.size(1) == Cin,
+               "conv2d_mfma_grouped: the weights must be packed channels-last bf16 CUDA tensors "
+               "of one shape [Cout, ", Cin, ", KH, KW]");
+  const int Cout = (int)w0.size(0), KH = (int)w0.size(2), KW = (int)w0.size(3);
+  IAMD_CHECK(ph >= 0 && pw >= 0, "conv2d_mfma_grouped: bad geometry");
+  const int Ho = H + 2 * (int)ph - KH + 1, Wo = W + 2 * (int)pw - KW + 1;
+  ConvArgs a;
+  a.x = reinterpret_cast<const __hip_bfloat16*>(x.data_ptr());
+  a.w = nullptr; a.bias = nullptr; a.y = nullptr;
+  a.xbytes = (int)(x.numel() * 2);
+  a.wbytes = (int)(w0.numel() * 2);
+  a.nz = 1; a.xbs = a.wbs = a.ybs = 0; a.bbs = 0;
+  a.ldy = Cout;
+  a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
+  a.KH = KH; a.KW = KW; a.sh = a.sw = 1; a.ph = (int)ph; a.pw = (int)pw; a.dh = a.dw = 1;
+  a.M = B * Ho * Wo;
+  a.cpt = Cin / kBK;
+  a.nk = KH * KW * a.cpt;
+  a.slope = (float)slope;
+  a.omode = 0;
+  a.oH = Ho; a.oW = Wo; a.osy = 1; a.osx = 1; a.ory = 0; a.orx = 0;
+  a.res = nullptr;
+  a.part = nullptr;
+  // declined unless every member alone would take the default v4 route (run_conv) with the
+  // prefetching tap step: the same tile, so the same bits at the same split
+  int ver = 0;
+  if (const char* e = std::getenv("IMAGINAIRE_AMD_CONV_V")) ver = std::atoi(e);
+  const char* pfe = std::getenv("IMAGINAIRE_AMD_V4_PF");
+  const bool fits = Ho > 0 && Wo > 0 && G <= kMaxConvGroups && KH * KW <= 64 &&
+                    (int64_t)B * H * W * Cin * 2 < kOobOffset && w0.numel() * 2 < kOobOffset &&
+                    (int64_t)B * Ho * Wo * Cout < (1ll << 31);
+  if (!fits || !(ver == 0 || ver == 4) || (ver == 0 && v5_eligible(a)) || !v4_eligible(a) ||
+      (pfe != nullptr && pfe[0] == '0'))
+    return {};
+  ConvGroupTab t;
+  std::vector<at::Tensor> ys, keep;
+  for (int g = 0; g < kMaxConvGroups; ++g) {
+    t.w[g] = nullptr; t.bias[g] = nullptr; t.ascale[g] = nullptr; t.y[g] = nullptr;
+  }
+  for (int g = 0; g < G; ++g) {
+    t.w[g] = reinterpret_cast<const __hip_bfloat16*>(ws[g].data_ptr());
+    if (!biases.empty()) {
+      IAMD_CHECK(biases[g].is_cuda() && biases[g].numel() == Cout,
+                 "conv2d_mfma_grouped: bias size");
+      keep.push_back(biases[g].to(at::kFloat).contiguous());
+      t.bias[g] = keep.back().data_ptr<float>();
+    }
+    if (!ascales.empty()) t.ascale[g] = ascale_ptr(ascales[g], "conv2d_mfma_grouped");
+    ys.push_back(at::empty({B, Cout, Ho, Wo},
+                           x.options().memory_format(at::MemoryFormat::ChannelsLast)));
+    t.y[g] = reinterpret_cast<__hip_bfloat16*>(ys.back().data_ptr());
+  }
+  g_last_conv_variant = 4;
+  run_v4_grouped(a, t, G, x);
+  return ys;
 }
 
 at::Tensor conv_weight_flip_t(const at::Tensor& w, int64_t s, int64_t qy, int64_t qx, int64_t nb);

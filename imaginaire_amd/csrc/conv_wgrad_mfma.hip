@@ -1044,6 +1044,22 @@ at::Tensor wgrad_finalize_sn(const at::Tensor& part, int64_t S, int64_t Cop, int
                              int64_t Cout, int64_t Cin, int64_t KH, int64_t KW,
                              const at::Tensor& dotp, const at::Tensor& u, const at::Tensor& v,
                              const at::Tensor& sigma, const c10::optional<at::Tensor>& dst);
+std::vector<at::Tensor> wgrad_finalize_grouped(
+    const at::Tensor& part, int64_t S, int64_t ng, int64_t Cpg, int64_t Cip, int64_t Cout,
+    int64_t Cin, int64_t KH, int64_t KW, const std::vector<std::vector<at::Tensor>>& sn,
+    const at::Tensor& dotp, int64_t gx, int64_t T, int64_t nNt, int64_t nCt,
+    const std::vector<c10::optional<at::Tensor>>& dsts);
+
+// A grouped weight gradient (conv2d_wgrad_mfma_grouped): dy is the channel concatenation of n
+// convs' output gradients (Cout / n channels each, a multiple of 128), x their shared input. The
+// k11 launch is the ordinary one on the concatenated dy, always into slabs; sn[g] = {shadow, u,
+// v, sigma} per group (or sn empty), dst[g] the optional destinations, out: the n gradients.
+struct WgradGroup {
+  int n = 0;
+  std::vector<std::vector<at::Tensor>> sn;
+  std::vector<c10::optional<at::Tensor>> dst;
+  std::vector<at::Tensor> out;
+};
 
 // dW [out_cout, out_cin, KH, KW] (channels-last memory = [Cout][KH][KW][Cin]) in fp32, or bf16
 // when out_bf16; out_cout / out_cin < 0 keep the (padded) channel counts of dy / x. Cropping
@@ -1081,7 +1097,7 @@ static at::Tensor wgrad_run(const at::Tensor& dy, const at::Tensor& x, int64_t K
                             int64_t nb, int64_t variant,
                             const c10::optional<std::vector<at::Tensor>>& sn,
                             const c10::optional<at::Tensor>& dst, int64_t pad_mode,
-                            py::dict* plan) {
+                            py::dict* plan, WgradGroup* grp = nullptr) {
   IAMD_CHECK(dy.is_cuda() && x.is_cuda(), "conv2d_wgrad_mfma: CUDA tensors expected");
   IAMD_CHECK(dy.scalar_type() == at::kBFloat16 && x.scalar_type() == at::kBFloat16,
              "conv2d_wgrad_mfma: bf16 operands expected");
@@ -1192,8 +1208,16 @@ static at::Tensor wgrad_run(const at::Tensor& dy, const at::Tensor& x, int64_t K
   }
   a.kps = ceil_div(a.nks, S);
   S = ceil_div(a.nks, a.kps);  // no empty split
-  const int64_t oc = out_cout < 0 ? Cout : out_cout, oi = out_cin < 0 ? Cin : out_cin;
-  IAMD_CHECK(oc <= Cout && oi <= Cin, "conv2d_wgrad_mfma: crop larger than the operands");
+  // (grouped: out_cout is one group's channel count, Cpg its share of dy's channels)
+  const int64_t Cpg = grp != nullptr ? Cout / std::max(1, grp->n) : Cout;
+  const int64_t oc = out_cout < 0 ? Cpg : out_cout, oi = out_cin < 0 ? Cin : out_cin;
+  IAMD_CHECK(oc <= Cpg && oi <= Cin, "conv2d_wgrad_mfma: crop larger than the operands");
+  IAMD_CHECK(grp == nullptr ||
+                 (grp->n >= 1 && nb == 1 && Cpg * grp->n == Cout && Cpg % 128 == 0 && oc == Cpg &&
+                  !sn.has_value() && !dst.has_value() && !out_bf16 &&
+                  (grp->sn.empty() || (int)grp->sn.size() == grp->n)),
+             "conv2d_wgrad_mfma_grouped: dy must hold n x (a multiple of 128) channels, every "
+             "one a real output channel, with one sn entry per group or none");
   // sn = {shadow bf16 [oc, oi, KH, KW] channels-last, u [oc], v [oi * KH * KW], sigma [1]}: the
   // weight is spectrally normalised and dW is the gradient w.r.t. the fp32 parameter W of
   // W / sigma (reference torch.nn.utils.spectral_norm, u / v constant):
@@ -1232,7 +1256,30 @@ static at::Tensor wgrad_run(const at::Tensor& dy, const at::Tensor& x, int64_t K
       }
     }
   }
-  const bool direct = !use_sn && S == 1 && !out_bf16 && oc == Cout && oi == Cin;
+  // grouped with SN: the epilogue's <G, W> reads the groups' shadows as one [Cout][KK][oi]
+  // weight (every block's n-tile lies in one group: its partial belongs to that group alone)
+  at::Tensor gshadow;
+  if (grp != nullptr && !grp->sn.empty()) {
+    std::vector<at::Tensor> sh;
+    for (const auto& e : grp->sn) {
+      IAMD_CHECK(e.size() == 4 && e[0].is_cuda() && e[0].scalar_type() == at::kBFloat16 &&
+                     e[0].dim() == 4 && e[0].size(0) == oc && e[0].size(1) == oi &&
+                     e[0].size(2) == KH && e[0].size(3) == KW &&
+                     e[0].is_contiguous(at::MemoryFormat::ChannelsLast),
+                 "conv2d_wgrad_mfma_grouped: sn[g] = [shadow bf16 [out_cout, out_cin, KH, KW] "
+                 "channels-last, u, v, sigma]");
+      sh.push_back(e[0]);
+    }
+    a.wsn_cout = Cout;
+    a.wsn_cin = (int)oi;
+    if (plan == nullptr) {
+      gshadow = at::cat(sh, 0).contiguous(at::MemoryFormat::ChannelsLast);
+      a.wsn = reinterpret_cast<const __hip_bfloat16*>(gshadow.data_ptr());
+      dotp = at::empty({(int64_t)tiles * S}, x.options().dtype(at::kFloat));
+      a.dotp = dotp.data_ptr<float>();
+    }
+  }
+  const bool direct = grp == nullptr && !use_sn && S == 1 && !out_bf16 && oc == Cout && oi == Cin;
   // IMAGINAIRE_AMD_WGRAD_EPILOGUE (read per call): 0 = the dword epilogue and the slab +
   // wgrad_finalize path everywhere, as before the restaged epilogue; 1 = the restaged epilogue
   // everywhere (A/B switch, tests); unset or empty = the default below; anything else is an error
@@ -1246,7 +1293,9 @@ static at::Tensor wgrad_run(const at::Tensor& dy, const at::Tensor& x, int64_t K
   // writes the finished dW (crop, cast, or the SN backward from the given <G, W> partials) and
   // no slab or finalize pass exists. With the 4-element sn, <G, W> comes from this launch's own
   // epilogue and is complete only after every block: that case keeps the second pass.
-  const bool fin = !epi_off && S == 1 && nb == 1 && !direct && (!use_sn || sn->size() == 5);
+  // (a grouped launch always writes slabs: its finalize pass splits them among the groups)
+  const bool fin = grp == nullptr && !epi_off && S == 1 && nb == 1 && !direct &&
+                   (!use_sn || sn->size() == 5);
   // Slabs (and the plain fp32 single slab) keep the dword epilogue in every family: switched
   // within one build the restaged one measured 0-8% slower on them
   // (profiles/wgrad_epilogue_probe_mi355x.txt)
@@ -1411,6 +1460,13 @@ static at::Tensor wgrad_run(const at::Tensor& dy, const at::Tensor& x, int64_t K
   else launch(I64(), I64());
   IAMD_LAUNCH_CHECK();
   if (direct || fin) return dW;
+  if (grp != nullptr) {
+    std::vector<std::vector<at::Tensor>> uvs;
+    for (const auto& e : grp->sn) uvs.push_back({e[1], e[2], e[3]});
+    grp->out = wgrad_finalize_grouped(part, S, grp->n, Cpg, Cin, oc, oi, KH, KW, uvs, dotp, gx,
+                                      (mt || v2) ? KH : KK, a.nNt, a.nCt, grp->dst);
+    return at::Tensor();
+  }
   if (use_sn)
     return wgrad_finalize_sn(part, S, Cout, Cin, oc, oi, KH, KW, dotp, (*sn)[1].contiguous(),
                              (*sn)[2].contiguous(), (*sn)[3], dst);
@@ -1429,6 +1485,29 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& dy, const at::Tensor& x, int64_t 
                              const c10::optional<at::Tensor>& dst, int64_t pad_mode) {
   return wgrad_run(dy, x, KH, KW, sh, sw, ph, pw, dh, dw, out_cout, out_cin, out_bf16, nb, variant,
                    sn, dst, pad_mode, nullptr);
+}
+
+// The weight gradients of n stride-1 convs that share the input x, from the channel
+// concatenation dy [B, n * C, Ho, Wo] of their output gradients (C % 128 == 0, every channel
+// real): ONE k11 launch (the kernel and split conv2d_wgrad_plan names for the same dy and x:
+// it is the ordinary launch with Cout = n * C) and one finalize pass that writes each group's
+// fp32 dW [C, out_cin, KH, KW] (into dsts[g] when given). sns: empty, or per group [shadow, u, v,
+// sigma] — the spectral-norm backward per group, <G, W> from the k11 epilogue.
+std::vector<at::Tensor> conv2d_wgrad_mfma_grouped(
+    const at::Tensor& dy, const at::Tensor& x, int64_t n, int64_t KH, int64_t KW, int64_t ph,
+    int64_t pw, int64_t out_cin, int64_t variant, const std::vector<std::vector<at::Tensor>>& sns,
+    const std::vector<c10::optional<at::Tensor>>& dsts) {
+  IAMD_CHECK(n >= 1 && dy.dim() == 4 && dy.size(1) % n == 0,
+             "conv2d_wgrad_mfma_grouped: dy channels must be n equal groups");
+  IAMD_CHECK(dsts.empty() || (int64_t)dsts.size() == n,
+             "conv2d_wgrad_mfma_grouped: one destination (or None) per group");
+  WgradGroup g;
+  g.n = (int)n;
+  g.sn = sns;
+  g.dst = dsts;
+  wgrad_run(dy, x, KH, KW, 1, 1, ph, pw, 1, 1, dy.size(1) / n, out_cin, false, 1, variant,
+            c10::nullopt, c10::nullopt, 0, nullptr, &g);
+  return g.out;
 }
 
 // What conv2d_wgrad_mfma would do for the same arguments, launching nothing: kernel (as

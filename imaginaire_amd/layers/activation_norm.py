@@ -30,13 +30,54 @@ from .conv import LinearBlock, Conv2dBlock, HyperConv2d, PartialConv2dBlock
 from .misc import PartialSequential
 
 
+class _LabelGroup(object):
+    """What one forward knows about the SPADE layers that read one resized label map."""
+    __slots__ = ('label_map', 'asked', 'ran', 'out')
+
+    def __init__(self, label_map):
+        self.label_map = label_map  # (kept alive: the group is keyed by its id)
+        self.asked = []             # (SpatiallyAdaptiveNorm, condition index) in call order
+        self.ran = False            # the grouped launch of this map was decided (run or not)
+        self.out = {}               # (id(module), index) -> hidden map not yet taken
+
+
+def _label_conv(mod, i):
+    """The first conv block of ``mod.mlps[i]`` when it is a plain conv + leaky / relu pair that
+    ``ops.conv.conv2d_act`` runs (the label MLP's first layer), else None."""
+    from .nonlinearity import act_slope
+    from .conv import _fusible_conv
+    mlp = mod.mlps[i]
+    if mod.partial[i] or len(mlp) != (1 if mod.separate_projection else 2):
+        return None
+    blk = mlp[0]
+    if type(blk) is not Conv2dBlock or list(blk.layers.keys()) != ['conv', 'nonlinearity']:
+        return None
+    conv = blk.layers['conv']
+    if type(conv) is not nn.Conv2d or not _fusible_conv(conv) or conv.groups != 1 or \
+            act_slope(blk.layers['nonlinearity']) is None:
+        return None
+    return blk
+
+
+def _label_conv_sig(blk):
+    """What two label convs must agree in to share a grouped launch."""
+    from .nonlinearity import act_slope
+    c = blk.layers['conv']
+    return (c.in_channels, c.out_channels, c.kernel_size, c.stride, c.padding, c.dilation,
+            c.bias is None, act_slope(blk.layers['nonlinearity']), c.training,
+            c.bias.device if c.bias is not None else None)
+
+
 class LabelMapCache(object):
-    """Per-forward cache of resized conditional maps keyed by (id, size)."""
+    """Per-forward cache of resized conditional maps keyed by (id, size), and of the hidden maps
+    of the SPADE label MLPs that one grouped conv launch computed for several layers at once
+    (``hidden``)."""
 
     _active = None
 
     def __init__(self):
         self.store = {}
+        self.groups = {}
 
     def __enter__(self):
         self._prev = LabelMapCache._active
@@ -46,6 +87,64 @@ class LabelMapCache(object):
     def __exit__(self, *args):
         LabelMapCache._active = self._prev
         self.store = {}
+        groups, self.groups = self.groups, {}
+        # learn, for the layer that asked first at each map, which layers followed it: the next
+        # forward computes their hidden maps together with its own
+        for g in groups.values():
+            members = []
+            for m in g.asked:
+                if not any(m[0] is o[0] and m[1] == o[1] for o in members):
+                    members.append(m)
+            (mod, i), size = members[0], tuple(g.label_map.shape[2:])
+            sig = _label_conv_sig(mod.mlps[i][0])
+            members = [m for m in members if _label_conv_sig(m[0].mlps[m[1]][0]) == sig]
+            mod.__dict__.setdefault('_label_groups', {})[(i, size)] = \
+                members if len(members) >= 2 else None
+
+    class suspended(object):
+        """Context in which no cache is active (a checkpointed block: its recompute runs outside
+        the generator's cache, so its first pass must not take part in a grouped launch)."""
+
+        def __enter__(self):
+            self._prev = LabelMapCache._active
+            LabelMapCache._active = None
+
+        def __exit__(self, *args):
+            LabelMapCache._active = self._prev
+
+    def hidden(self, mod, i, label_map):
+        """``mod.mlps[i][0](label_map)``. The first layer to ask at a map whose followers are
+        known from an earlier forward computes all their hidden maps in one grouped conv
+        (ops/conv.py ``conv2d_act_group``); the followers take theirs from here."""
+        from .conv import _plain_conv_weight
+        blk = mod.mlps[i][0]
+        g = self.groups.get(id(label_map))
+        if g is None:
+            g = self.groups[id(label_map)] = _LabelGroup(label_map)
+        g.asked.append((mod, i))
+        out = g.out.pop((id(mod), i), None)
+        if out is not None:
+            return out
+        members = None
+        if not g.ran:
+            g.ran = True
+            members = mod.__dict__.get('_label_groups', {}).get(
+                (i, tuple(label_map.shape[2:])))
+        if members and nhwc_conv.spade_group_enabled():
+            # verify what was learned: the same first layer, every member still a label conv
+            # that agrees with it
+            blks = [_label_conv(m, j) for m, j in members]
+            if members[0][0] is mod and members[0][1] == i and all(
+                    b is not None and _label_conv_sig(b) == _label_conv_sig(blk) for b in blks):
+                convs = [b.layers['conv'] for b in blks]
+                c0 = convs[0]
+                ys = nhwc_conv.conv2d_act_group(
+                    label_map, [_plain_conv_weight(c) for c in convs], [c.bias for c in convs],
+                    c0.stride, c0.padding, c0.dilation, _label_conv_sig(blk)[7])
+                for (m, j), y in zip(members[1:], ys[1:]):
+                    g.out[(id(m), j)] = y
+                return ys[0]
+        return blk(label_map)
 
     @staticmethod
     def resize(t, size, mode='nearest', conv_pad=False):
@@ -383,18 +482,34 @@ class SpatiallyAdaptiveNorm(nn.Module):
         self.norm = get_activation_norm_layer(num_features, activation_norm_type, 2,
                                               **vars(activation_norm_params))
         self.conditional = True
+        # (condition index, map size) -> the [(norm, index)] whose label MLPs read the map this
+        # layer is the first to ask for, learned by LabelMapCache from the previous forward
+        self._label_groups = {}
+
+    def _hidden(self, i, label_map):
+        """The label MLP's hidden map ``mlps[i][0](label_map)``: inside an active
+        :class:`LabelMapCache` the layers of one resolution compute theirs in one grouped conv
+        launch (``IMAGINAIRE_AMD_SPADE_GROUP=0``: each its own)."""
+        cache = LabelMapCache._active
+        if cache is None or not nhwc_conv.spade_group_enabled() or \
+                _label_conv(self, i) is None:
+            return self.mlps[i][0](label_map)
+        return cache.hidden(self, i, label_map)
 
     def _gb(self, i, label_map):
         """γ|β for condition i as one [N, 2C, H, W] tensor (first C = γ)."""
         if self.separate_projection:
             from .weight_norm import get_weight
-            hidden = self.mlps[i](label_map)
+            hidden = self._hidden(i, label_map) if len(self.mlps[i]) == 1 else \
+                self.mlps[i](label_map)
             cg = self.gammas[i].layers.conv
             cb = self.betas[i].layers.conv
             w = cat0(get_weight(cg), get_weight(cb))
             b = torch.cat([cg.bias, cb.bias], 0) if cg.bias is not None else None
             return nhwc_conv.conv2d(hidden, w, b, cg.stride, cg.padding, cg.dilation, cg.groups,
                                     cg.padding_mode)
+        if len(self.mlps[i]) == 2 and not self.partial[i]:
+            return self.mlps[i][1](self._hidden(i, label_map))
         return self.mlps[i](label_map)
 
     def forward(self, x, *cond_inputs, act_slope=1.0, **kwargs):

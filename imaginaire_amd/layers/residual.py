@@ -105,8 +105,12 @@ class _BaseResBlock(nn.Module):
                 x_shortcut = x
             return self.conv_block_1(dx, *cond_inputs, residual=x_shortcut, **kw_cond_inputs)
         if do_checkpoint:
-            dx = checkpoint(self.conv_blocks, x, *cond_inputs, use_reentrant=False,
-                            **kw_cond_inputs)
+            # (no label-map cache inside: the recompute runs after the generator's cache is gone,
+            # and both passes must launch the same convs)
+            from .activation_norm import LabelMapCache
+            with LabelMapCache.suspended():
+                dx = checkpoint(self.conv_blocks, x, *cond_inputs, use_reentrant=False,
+                                **kw_cond_inputs)
         else:
             dx = self.conv_blocks(x, *cond_inputs, **kw_cond_inputs)
         if self.learn_shortcut:

@@ -1676,6 +1676,195 @@ def conv2d_act(x, weight, bias=None, stride=1, padding=0, dilation=1, slope=1.0)
                 'zeros', None, slope)
 
 
+class _MfmaConvGroup(torch.autograd.Function):
+    """``n`` stride-1 :class:`_MfmaConv2d` convs of ONE input that needs no gradient (the first
+    conv of every SPADE label MLP at one resolution), forward in one grouped k10 launch
+    (csrc/conv_mfma.hip ``conv2d_mfma_grouped``): each conv alone has one 128-channel n-tile, so
+    below 128 x 256 its grid leaves most of the chip idle and splits K with a reduce launch of
+    its own. ``params`` = the n weights, then the n biases (or none); ``sws[g]``: the weight's
+    :class:`SNWeight` (then ``params[g]`` is its fp32 W) or None. n outputs, each its own dense
+    NHWC tensor. Where the native entry declines, the forward launches the convs one by one as
+    :class:`_MfmaConv2d` does.
+
+    The backward runs once, after the last output's gradient has arrived, and per member exactly
+    what :class:`_MfmaConv2d` runs without a data gradient (k2, then k11 with the spectral-norm
+    backward and the DDP bucket destination); a member whose output got no gradient gets None."""
+
+    @staticmethod
+    def forward(ctx, x, padding, slope, sws, *params):
+        n = len(sws)
+        ws, bs = params[:n], params[n:]
+        cout, cin, kh, kw = ws[0].shape
+        cp = _round_up(cin, 64)
+        X = _ext.ext()
+        xb = _pad_channels(x, cp, torch.bfloat16)
+        wbs, bps, sigs = [], [], []
+        for w, sw in zip(ws, sws):
+            if sw is None:
+                wbs.append(_frozen_prep(w, ('w', cp, cout),
+                                        lambda w=w: _pad_channels(w, cp, torch.bfloat16)))
+            else:
+                wbs.append(_pad_channels(sw.shadow, cp, torch.bfloat16))
+                sigs.append(sw.sigma.reshape(1))
+        for b in bs:
+            bps.append(_frozen_prep(b, ('b', cout), lambda b=b: b.float()))
+        ho, wo = _out_hw(x.shape[2], x.shape[3], (kh, kw), (1, 1), padding, (1, 1))
+        fl = 2.0 * x.shape[0] * ho * wo * cout * cp * kh * kw
+        desc = _gemm_desc(xb, wbs[0], (1, 1), padding) + ('' if sws[0] is None else ' sn')
+        with _Logged('fwd', 'k10g', n * fl, '%s g%d' % (desc, n)) as lg:
+            ys = X.conv2d_mfma_grouped(xb, wbs, bps, sigs, padding[0], padding[1], float(slope))
+            if not ys:
+                lg.rec = None
+        ctx.grouped = bool(ys)
+        if not ys:  # not grouped (a shape the v4 tile refuses): one by one, as _MfmaConv2d
+            ys = []
+            for g in range(n):
+                with _Logged('fwd', 'k10', fl, desc):
+                    ys.append(X.conv2d_mfma(xb, wbs[g], bps[g] if bps else None, 1, 1,
+                                            padding[0], padding[1], 1, 1, float(slope), 1, cout,
+                                            None, sigs[g] if sigs else None, 0))
+        ctx.n = n
+        ctx.conf = (padding, float(slope), cin, cout, x.shape[1],
+                    [w.dtype for w in ws], [b.dtype for b in bs])
+        ctx.sn = [None if sw is None else (sw.shadow, sw.u, sw.v, sw.sigma.reshape(1))
+                  for sw in sws]
+        ctx.wparams = [w if (isinstance(w, torch.nn.Parameter) and w.dtype == torch.float32)
+                       else None for w in ws]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xb, *wbs, *(ys if slope != 1.0 else ()))
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        xb, wbs, ys = saved[0], saved[1:1 + n], saved[1 + n:]
+        padding, slope, cin, cout, xc, wdts, bdts = ctx.conf
+        st = dl = (1, 1)
+        dws, dbs = [None] * n, [None] * len(bdts)
+        grouped = _MfmaConvGroup._backward_grouped(ctx, dys, xb, wbs, ys)
+        if grouped is not None:
+            return (None, None, None, None) + grouped
+        for g in range(n):
+            dy = dys[g]
+            need_w = ctx.needs_input_grad[4 + g]
+            need_b = bool(bdts) and ctx.needs_input_grad[4 + n + g]
+            if dy is None or not (need_w or need_b):
+                continue
+            wb, sn = wbs[g], ctx.sn[g]
+            r = _bwd_route(tuple(dy.shape), tuple(xb.shape), tuple(wb.shape), st, padding, dl, 0,
+                           slope, False, need_w, need_b, sn is not None, xc, cout, False)
+            dy, dy_b, db = _act_bias_bwd(ys[g] if ys else None, dy, slope, r.db == 'last',
+                                         wb.shape[0])
+            dw = None
+            if need_w:
+                dest = _take_grad_dest(ctx.wparams[g], (cout, cin, wb.shape[2], wb.shape[3]))
+                dw = _wgrad(dy, xb, wb, st, padding, dl, cout, cin, wdts[g], sn, dest)
+            if r.db == 'last':
+                db = _bias_grad(dy_b)
+            dws[g], db = _finish_grads(dw, db, cout, cin, wdts[g], bdts[g] if bdts else None,
+                                       need_b)
+            if bdts:
+                dbs[g] = db
+        return (None, None, None, None) + tuple(dws) + tuple(dbs)
+
+    @staticmethod
+    def _backward_grouped(ctx, dys, xb, wbs, ys):
+        """The members' backward as one k2 launch, one k11 launch and one finalize pass (csrc
+        ``bias_act_bwd_grouped``, ``conv2d_wgrad_mfma_grouped``): the activation backward writes
+        every member's dz into its channel slice of one buffer, the members' weight gradients
+        are ONE GEMM over it (they share x), and the finalize pass applies each member's
+        spectral-norm backward and writes into its own (DDP bucket) destination. Returns the
+        parameter gradients, or None where a member has no gradient, the forward was not
+        grouped or the weight-gradient choice is not k11: the caller then goes one by one."""
+        n = ctx.n
+        padding, slope, cin, cout, xc, wdts, bdts = ctx.conf
+        need = ctx.needs_input_grad
+        if not ctx.grouped or slope == 1.0 or any(dy is None for dy in dys) or \
+                not all(need[4:4 + n]) or (bdts and not all(need[4 + n:4 + 2 * n])) or \
+                any(d != torch.float32 for d in wdts):
+            return None
+        st = dl = (1, 1)
+        has_sn = ctx.sn[0] is not None
+        kh, kw = wbs[0].shape[2], wbs[0].shape[3]
+        r = _bwd_route(tuple(dys[0].shape), tuple(xb.shape), tuple(wbs[0].shape), st, padding, dl,
+                       0, slope, False, True, bool(bdts), has_sn, xc, cout, False)
+        if r.db != 'act' or r.dgrad != 'none':
+            return None
+        # the variant choice, under the key of the concatenated GEMM (tune_pending times the
+        # ordinary k11 launch of that shape, which is the launch the group makes)
+        dshape = (dys[0].shape[0], n * cout) + tuple(dys[0].shape[2:])
+        key = WgradKey(dshape, tuple(xb.shape), (n * cout,) + tuple(wbs[0].shape[1:]), st,
+                       padding, dl, n * cout, cin, wdts[0], 'sn' if has_sn else None, 0)
+        X = _ext.ext()
+        variants = ('k11', 'k11v2') if X.conv2d_wgrad_v2_eligible(
+            torch.empty(dshape, dtype=torch.bfloat16, device='meta'), xb, kh, kw, 1, 1, 1, 1, 1,
+            0) else ('k11',)
+        label, run, pending = _wgrad_choice(key, _MFMA_WGRAD, variants, _capturing(), has_sn)
+        if run == 'miopen':
+            return None
+        if pending:
+            _WGRAD_PENDING.setdefault(key, (torch.bfloat16, xb.dtype, wbs[0].dtype))
+        dz, db = X.bias_act_bwd_grouped(
+            list(ys), [_pad_channels(dy, cout, torch.bfloat16) for dy in dys], slope)
+        dests = [_take_grad_dest(p, (cout, cin, kh, kw)) for p in ctx.wparams]
+        sns = [list(s) for s in ctx.sn] if has_sn else []
+        with _Logged('wgrad', label + 'g', 2.0 * dz.shape[0] * dz.shape[2] * dz.shape[3] * n *
+                     wbs[0].numel(), '%s g%d' % (_gemm_desc(xb, wbs[0], st, padding), n)):
+            dws = X.conv2d_wgrad_mfma_grouped(dz, xb, n, kh, kw, padding[0], padding[1], cin,
+                                              run, sns, dests)
+        outs_w, outs_b = [], []
+        for g in range(n):
+            dw, dbg = _finish_grads(dws[g], db[g * cout:(g + 1) * cout] if bdts else None, cout,
+                                    cin, wdts[g], bdts[g] if bdts else None, bool(bdts))
+            outs_w.append(dw)
+            if bdts:
+                outs_b.append(dbg)
+        return tuple(outs_w) + tuple(outs_b)
+
+
+def spade_group_enabled():
+    """``IMAGINAIRE_AMD_SPADE_GROUP`` (read per call; 0: every SPADE label conv is launched on
+    its own, the A/B switch of the grouped launch)."""
+    return os.environ.get('IMAGINAIRE_AMD_SPADE_GROUP', '1') != '0'
+
+
+def _run_group(x, ws, sws, bs, padding, slope):
+    """The grouped executor (a seam the CPU tests replace)."""
+    return _MfmaConvGroup.apply(x, padding, slope, sws, *ws, *bs)
+
+
+def conv2d_act_group(x, weights, biases, stride=1, padding=0, dilation=1, slope=1.0):
+    """``[conv2d_act(x, w, b, ...) for w, b in zip(weights, biases)]`` for convs that share their
+    input. Where the planner sends every member down the same plain k10 route (stride 1,
+    undilated, zero padding read by the loader, Cout a multiple of 128, all weights fused
+    spectral-norm references or all plain tensors, no gradient asked of ``x``) and the switch is
+    on, they run as one :class:`_MfmaConvGroup`; else one by one, exactly as ``conv2d_act``."""
+    st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
+    rs = [_route(x, w, st, pd, dl, slope=slope) for w in weights]
+
+    def one_by_one():
+        return [_run(r, x, w, b, st, pd, dl, 1, 'zeros', None, slope)
+                for r, w, b in zip(rs, weights, biases)]
+
+    r0 = rs[0]
+    sn = [isinstance(w, SNWeight) for w in weights]
+    shapes = [tuple((w.shadow if s else w).shape) for w, s in zip(weights, sn)]
+    if not (len(weights) >= 2 and spade_group_enabled() and all(r == r0 for r in rs) and
+            r0.kind == 'k10' and not r0.pmode and not r0.pad_first and st == (1, 1) and
+            dl == (1, 1) and all(s == shapes[0] for s in shapes) and shapes[0][0] % 128 == 0 and
+            all(s == sn[0] for s in sn) and r0.sn_fused == sn[0] and
+            all((b is None) == (biases[0] is None) for b in biases) and
+            not (x.requires_grad and torch.is_grad_enabled())):
+        return one_by_one()
+    if sn[0]:
+        ws, sws = [w.W for w in weights], tuple(weights)
+    else:
+        ws, sws = [_match_channels(x, w) for w in weights], (None,) * len(weights)
+    bs = [] if biases[0] is None else list(biases)
+    return list(_run_group(x, ws, sws, bs, pd, slope))
+
+
 _DECONV_MIN_PIX = int(os.environ.get('IMAGINAIRE_AMD_DECONV_MIN_PIX', 4096))
 _DECONV_CHOICE = {}
 _DECONV_PENDING = {}
