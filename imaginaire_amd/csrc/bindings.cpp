@@ -121,6 +121,12 @@ at::Tensor part_bbox(const at::Tensor& label, std::vector<int64_t> channels, int
 at::Tensor roi_crop_fwd(const at::Tensor& image, const at::Tensor& boxes, int64_t oh,
                         int64_t ow);
 at::Tensor roi_crop_bwd(const at::Tensor& dy, const at::Tensor& boxes, const at::Tensor& like);
+// splat.hip (k18 point-cloud splat renderer)
+void splat_update(const at::Tensor& image, const at::Tensor& rows, const at::Tensor& counts,
+                  at::Tensor& color, at::Tensor& seen_time, at::Tensor& counters,
+                  at::Tensor& win_pt);
+at::Tensor splat_render(const at::Tensor& rows, const at::Tensor& counts, const at::Tensor& color,
+                        at::Tensor& counters, at::Tensor& win_px, int64_t h, int64_t w);
 // flow_warp.hip (k9 warp, k7 resample2d)
 at::Tensor flow_warp_fwd(const at::Tensor& img, const at::Tensor& flow);
 std::vector<at::Tensor> flow_warp_bwd(const at::Tensor& img, const at::Tensor& flow,
@@ -408,6 +414,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("roi_crop_fwd", &iamd::roi_crop_fwd,
         "crop to device boxes + bilinear resize of the last 3 channels (k17)");
   m.def("roi_crop_bwd", &iamd::roi_crop_bwd, "k17 backward (gather over the whole image)");
+  m.def("splat_update", &iamd::splat_update,
+        "colour the unseen listed points of a device point cloud from an image, in place (k18)");
+  m.def("splat_render", &iamd::splat_render,
+        "guidance image + seen mask [B, 4, h, w] of the listed points (k18)");
   m.def("flow_warp_fwd", &iamd::flow_warp_fwd, "bilinear flow warp, border (k9)");
   m.def("flow_warp_bwd", &iamd::flow_warp_bwd, "k9 backward", py::arg("img"), py::arg("flow"),
         py::arg("dout"), py::arg("need_dimg") = true);

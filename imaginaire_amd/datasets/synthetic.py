@@ -110,6 +110,53 @@ class Dataset(torch.utils.data.Dataset):
         self.num_classes = getattr(self.cfg_data, 'num_classes', 0)
         self.sample_class_idx = None
         self.num_style_classes = int(getattr(self.cfg_data, 'num_style_classes', 0) or 0) or 1
+        # wc-vid2vid point lists (``unprojections``): rows per frame; 0 = none, as before
+        self.unprojection_points = int(getattr(syn, 'unprojection_points', 0) or 0) \
+            if syn is not None else 0
+        self._world = None
+
+    # pixels the synthetic camera moves per frame over the world of point ids
+    WORLD_SCROLL = 3
+
+    def _unprojections(self, index, num_frames):
+        """Point lists of a sequence in the reference's padded layout
+        ``{'w{W}xh{H}': int64 [T, N + 1, 3]}`` (rows ``(i, j, point id)`` padded with -1, the
+        last row the frame's length; model_utils/wc_vid2vid/render.py decode_unprojections).
+
+        One fixed seeded world of point ids, ``h`` x ``(w + scroll * max frames)``, scrolls
+        under the frame by ``WORLD_SCROLL`` pixels per frame, so successive frames share most
+        ids (already coloured: mask 1) and bring in some new ones. A frame lists a random
+        subset of its pixels plus 1/8 duplicates: half of them a pixel listed twice (with
+        another point), half a point listed twice (at another pixel). Drawn from a generator
+        of its own: the rest of the batch is what it is without the lists."""
+        h, w = self.h, self.w
+        if self._world is None:
+            width = w + self.WORLD_SCROLL * self.sequence_length_max
+            world = torch.Generator().manual_seed(4321)
+            self._world = torch.randperm(h * width, generator=world).view(h, width)
+        gen = torch.Generator().manual_seed(777 + int(index))
+        n_max = self.unprojection_points
+        out = torch.full((num_frames, n_max + 1, 3), -1, dtype=torch.int64)
+        for t in range(num_frames):
+            n = max(1, n_max - (t * 5) % 7)  # lengths differ a little: the padding is used
+            dup = n // 8
+            pix = torch.randint(0, h * w, (n,), generator=gen)
+            subset = torch.randperm(h * w, generator=gen)[:n - dup]
+            pix[:subset.numel()] = subset
+            i, j = pix // w, pix % w
+            ids = self._world[i, (j + self.WORLD_SCROLL * t) % self._world.shape[1]]
+            if dup:
+                src = torch.randint(0, n - dup, (dup,), generator=gen)
+                half = dup // 2
+                # a pixel listed twice: the source row's pixel with this row's own point
+                i[n - dup:n - dup + half] = i[src[:half]]
+                j[n - dup:n - dup + half] = j[src[:half]]
+                # a point listed twice: the source row's point at this row's own pixel
+                ids[n - dup + half:] = ids[src[half:]]
+            order = torch.randperm(n, generator=gen)
+            out[t, :n] = torch.stack([i, j, ids], 1)[order]
+            out[t, -1] = n
+        return {'w%dxh%d' % (w, h): out}
 
     def __len__(self):
         return self.length
@@ -220,6 +267,8 @@ class Dataset(torch.utils.data.Dataset):
                 (index * 7 + 3) % ncls
             data['labels_content'] = torch.tensor(index % ncls)
             data['labels_style'] = torch.tensor(style_cls % ncls)
+        if self.unprojection_points > 0 and self.seq_len:
+            data['unprojections'] = self._unprojections(index, self.seq_len)
         data['key'] = {k: ['synthetic/%06d' % index] for k in self.types}
         data['original_h_w'] = torch.tensor([self.h, self.w])
         data['is_flipped'] = False

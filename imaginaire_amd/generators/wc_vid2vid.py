@@ -4,23 +4,34 @@ vid2vid plus (a) an optional frozen single-image SPADE model that renders
 the first frame, (b) externally supplied flow + occlusion mask
 (``data['flow']`` / ``data['mask']`` — the fork's data contract, SURVEY
 Appendix A) instead of a learned temporal flow network, and (c) guidance
-images splatted from the accumulated 3-D point cloud (device-resident
-``SplatRenderer``) fed to SPADE as an extra (optionally partial-conv)
-condition.
+images splatted from the accumulated 3-D point cloud
+(``DeviceSplatRenderer``: fixed capacity, on the device, one cloud per
+sample of the batch) fed to SPADE as an extra (optionally partial-conv)
+condition. Rendering the guidance and colouring the cloud from the generated
+frame are kernel launches on device tensors with no host read, so the
+trainer's iteration is captured as a hipGraph.
 
 The fork forces ``unprojection = None`` (guidance off); here guidance is
 used whenever the data carries unprojections and ``gen.guidance.enabled`` is
 not false — with the fork's configs (no unprojections in the data) the
 behaviour is identical.
 """
-import numpy as np
 import torch
-import torch.nn.functional as F
 
 from imaginaire_amd.generators.vid2vid import Generator as Vid2VidGenerator
 from imaginaire_amd.model_utils.fs_vid2vid import resample
-from imaginaire_amd.model_utils.wc_vid2vid.render import SplatRenderer
-from imaginaire_amd.utils.visualization import tensor2im
+from imaginaire_amd.model_utils.wc_vid2vid.render import DEFAULT_MAX_POINTS, DeviceSplatRenderer
+
+
+def guidance_key(unprojections, h, w):
+    """The resolution key of the point lists to use for an ``h`` x ``w`` frame: the frame's own
+    when the data has it, else the one the reference hard-codes. Returns (key, h, w) with the
+    guidance size parsed from the key."""
+    key = 'w%dxh%d' % (w, h)
+    if key not in unprojections:
+        key = 'w1024xh512'
+    gw, gh = [int(v[1:]) for v in key.split('x')]
+    return key, gh, gw
 
 
 class Generator(Vid2VidGenerator):
@@ -32,8 +43,8 @@ class Generator(Vid2VidGenerator):
         self.guidance_partial_conv = getattr(self.guidance_cfg, 'partial_conv', False)
         self.guidance_enabled = getattr(self.guidance_cfg, 'enabled', True)
         super().__init__(gen_cfg, data_cfg)
-        self.renderer = SplatRenderer()
-        self.reset_renderer()
+        self.renderer = DeviceSplatRenderer(
+            getattr(self.guidance_cfg, 'max_points', DEFAULT_MAX_POINTS))
         self.single_image_model = None
         self.single_image_model_z = None
 
@@ -54,34 +65,17 @@ class Generator(Vid2VidGenerator):
             self.single_image_model = m.module if hasattr(m, 'averaged_model') else m
             self.single_image_model_z = None
 
-    def reset_renderer(self, is_flipped_input=False):
+    def reset_renderer(self):
+        """Forget the point cloud (in place: a captured graph keeps valid pointers)."""
         self.renderer.reset()
-        self.is_flipped_input = bool(is_flipped_input[0]) if isinstance(
-            is_flipped_input, (list, tuple, torch.Tensor)) else bool(is_flipped_input)
-        self.renderer_num_forwards = 0
         self.single_image_model_z = None
 
-    def renderer_update_point_cloud(self, image, point_info):
-        if point_info is None or len(point_info) == 0:
-            return
-        if isinstance(image, torch.Tensor):
-            image = tensor2im(image.detach())[0]
-        if self.is_flipped_input:
-            image = np.fliplr(image).copy()
-        self.renderer.update_point_cloud(image, point_info)
-        self.renderer_num_forwards += 1
-
-    def get_guidance_images_and_masks(self, unprojection, device):
-        resolution = 'w1024xh512'
-        point_info = unprojection[resolution]
-        w, h = [int(v[1:]) for v in resolution.split('x')]
-        image, mask = self.renderer.render_image(point_info, w, h, return_mask=True)
-        if self.is_flipped_input:
-            image, mask = np.fliplr(image).copy(), np.fliplr(mask).copy()
-        image = torch.from_numpy(image).permute(2, 0, 1).float().div(255).sub(0.5).mul(2)
-        mask = torch.from_numpy(mask).permute(2, 0, 1).float().div(255)
-        guidance = torch.cat((image, mask), dim=0).unsqueeze(0).to(device)
-        return guidance, point_info
+    def get_guidance_images_and_masks(self, unprojection):
+        """fp32 ``[B, 4, h, w]``: stored colour in [-1, 1] and seen mask of the frame's points,
+        one rendering per sample. ``unprojection``: the frame's ``rows`` / ``counts`` device
+        tensors and the guidance size ``hw`` (trainers/wc_vid2vid.py)."""
+        h, w = unprojection['hw']
+        return self.renderer.render(unprojection['rows'], unprojection['counts'], h, w)
 
     def forward(self, data):
         self._init_single_image_model()
@@ -94,9 +88,9 @@ class Generator(Vid2VidGenerator):
         flow = mask = img_warp = None
         warp_prev = self.temporal_initialized and not is_first_frame and \
             label_prev.shape[1] == self.num_frames_G - 1
-        guidance, point_info = None, None
+        guidance = None
         if unprojection is not None:
-            guidance, point_info = self.get_guidance_images_and_masks(unprojection, label.device)
+            guidance = self.get_guidance_images_and_masks(unprojection)
         cond_maps_now = self.get_cond_maps(label, self.label_embedding)
 
         if self.single_image_model is not None and not warp_prev:
@@ -133,7 +127,10 @@ class Generator(Vid2VidGenerator):
                 x_img = self.one_up_conv_layer(x_img, cond_maps, i)
             img_final = torch.tanh(self.conv_img(x_img))
             source = 'in_training'
-        self.renderer_update_point_cloud(img_final, point_info)
+        if unprojection is not None:
+            # whatever made the frame (the pretrained first-frame model too) colours the cloud
+            self.renderer.update(img_final.detach(), unprojection['rows'],
+                                 unprojection['counts'])
         return dict(fake_images=img_final, fake_flow_maps=flow, fake_occlusion_masks=mask,
                     fake_raw_images=None, warped_images=img_warp,
                     guidance_images_and_masks=guidance, fake_images_source=source)

@@ -2,20 +2,36 @@
 (reference model_utils/wc_vid2vid/render.py:11-199).
 
 The reference keeps the colour / seen-mask / first-seen-time arrays of the
-3-D point cloud in host numpy and re-renders per frame on the CPU. Here the
-arrays live on the device the frames live on (HBM on MI355X): updating the
-cloud with a new frame and splatting it into a guidance image are two
-index_put / gather launches, so guidance rendering never round-trips
-through the host.
+3-D point cloud in host numpy and re-renders per frame on the CPU. Two
+renderers live here:
 
-Semantics are unchanged: a point's colour is fixed the first time it is
-seen; rendering writes the stored colour of every visible point and a 255
-mask where the point has been seen. Duplicate targets (one point id listed
+* ``DeviceSplatRenderer`` is what the generator and the trainer use. Its
+  cloud has a fixed capacity and stays on the device (ops/splat.py, k18):
+  the frame's point list, its length, the generated frame and the guidance
+  image never visit the host, nothing is reallocated, and batch entries are
+  rendered per sample, so the training iteration is captured as a hipGraph
+  whose replays follow each batch's own points. What stays on the host: the
+  ``N > Rcap`` shape check of ``unprojections_to_rows`` (tensor shapes, no
+  device read) and ``num_points()`` / ``dropped()``, which read counters back
+  for logging outside the step.
+* ``SplatRenderer`` is the growing-array form of the reference with the
+  arrays held in device tensors. It takes host point lists, reads the
+  largest point id back to grow its arrays and returns numpy images, i.e. it
+  synchronises with the host on every call; it is kept as the behavioural
+  twin of the reference (tests/test_wc_render_cpu.py).
+
+Semantics are the reference's: a point's colour is fixed the first time it is
+seen; rendering writes the stored colour of every visible point and a mask
+where the point has been seen. Duplicate targets (one point id listed
 twice in a frame, two points projecting to one pixel) resolve as numpy's
 fancy-index assignment does — the LAST row wins (reference render.py:87-97,
-138) — by a scatter-max of row numbers that keeps only each target's winning
-row before a duplicate-free index_put (a plain device index_put with duplicate
-indices has an undefined write order).
+138). ``SplatRenderer`` gets there by a scatter-max of row numbers that keeps
+only each target's winning row before a duplicate-free index_put (a plain
+device index_put with duplicate indices has an undefined write order); the
+kernels by an integer atomic max of row numbers. The one difference of the
+device renderer: a row whose point id does not fit the capacity, or whose
+pixel lies outside the image, is dropped and counted instead of growing the
+arrays.
 """
 import json
 import os
@@ -95,6 +111,83 @@ class SplatRenderer(object):
             mask[i, j] = 255 * self.seen_mask[pid]
         output, mask = output.cpu().numpy(), mask.cpu().numpy()
         return (output, mask) if return_mask else output
+
+
+# Point slots per sample of the device renderer (gen.guidance.max_points). A slot costs three
+# int32 words (colour + seen flag, first-seen time, the update's winner word): 48 MiB per
+# sample at the default, plus 4 bytes per guidance pixel (2 MiB at 512 x 1024).
+DEFAULT_MAX_POINTS = 1 << 22
+
+
+class DeviceSplatRenderer(object):
+    """Fixed-capacity point cloud on the device (ops/splat.py). The state for
+    ``(batch, max_points, device)`` is allocated on first use and afterwards only modified in
+    place; ``update`` / ``render`` read nothing back."""
+
+    def __init__(self, max_points=DEFAULT_MAX_POINTS):
+        self.max_points = int(max_points)
+        self.state = None
+
+    def _state(self, batch, device):
+        s = self.state
+        if s is None or s.batch != batch or s.device != device:
+            from imaginaire_amd.ops.splat import SplatState
+            self.state = s = SplatState(batch, self.max_points, device)
+        return s
+
+    def reset(self):
+        """Forget every point: zeroes the state in place and keeps the storage."""
+        if self.state is not None:
+            self.state.reset()
+
+    def update(self, image, rows, counts):
+        """image ``[B, 3, H, W]`` in [-1, 1]; rows int32 ``[B, R, 3]`` = (i, j, point id);
+        counts int32 ``[B]`` valid leading rows."""
+        from imaginaire_amd.ops.splat import splat_update
+        splat_update(self._state(image.shape[0], image.device), image, rows, counts)
+
+    def render(self, rows, counts, h, w):
+        """fp32 ``[B, 4, h, w]`` guidance: colour in [-1, 1] and seen mask of the listed
+        points, ``-1, -1, -1, 0`` elsewhere."""
+        from imaginaire_amd.ops.splat import splat_render
+        return splat_render(self._state(rows.shape[0], rows.device), rows, counts, h, w)
+
+    # the only host reads: for logging, outside the training step
+    def num_points(self):
+        """Seen points per sample (list of int)."""
+        if self.state is None:
+            return []
+        return ((self.state.color >> 24) & 1).sum(1).tolist()
+
+    def dropped(self):
+        """Rows dropped so far per sample (point id beyond the capacity or pixel outside the
+        image), over updates and renders."""
+        return [] if self.state is None else self.state.counters[:, 1].tolist()
+
+
+def unprojections_to_rows(value, max_rows, width, is_flipped=None):
+    """The padded point lists of a batch, ``[B, T, N + 1, 3]`` (padded with -1, the last row of
+    each frame the length sentinel of ``decode_unprojections``), as what the device renderer
+    takes: rows int32 ``[B, T, max_rows, 3]`` and counts int32 ``[B, T]``, on ``value``'s
+    device, with nothing read back. ``is_flipped`` (bool, scalar or ``[B]``): the sample was
+    flipped horizontally, so its valid rows get ``j -> width - 1 - j`` (the reference flips
+    the frame before the update and the rendering after it: the same map, and a bijection, so
+    the last row still wins). ``N > max_rows`` raises ValueError (a shape check)."""
+    if value.dim() != 4 or value.shape[2] < 1 or value.shape[3] != 3:
+        raise ValueError('unprojections: [B, T, N + 1, 3] expected, got %s' % (tuple(value.shape),))
+    b, t, n = value.shape[0], value.shape[1], value.shape[2] - 1
+    if n > max_rows:
+        raise ValueError('unprojections hold up to %d rows per frame but gen.guidance.max_rows '
+                         'is %d' % (n, max_rows))
+    counts = value[:, :, -1, 0].clamp(0, n).to(torch.int32)
+    rows = torch.zeros(b, t, max_rows, 3, dtype=torch.int32, device=value.device)
+    body = value[:, :, :n].to(torch.int32)
+    if is_flipped is not None:
+        flip = torch.as_tensor(is_flipped, device=value.device).bool().reshape(-1, 1, 1)
+        valid = torch.arange(n, device=value.device).view(1, 1, n) < counts.unsqueeze(-1)
+        body[..., 1] = torch.where(valid & flip, width - 1 - body[..., 1], body[..., 1])
+    rows[:, :, :n] = body
+    return rows, counts
 
 
 def _load_item(item):
