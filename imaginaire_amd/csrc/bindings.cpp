@@ -11,7 +11,37 @@ std::vector<at::Tensor> norm_stats(const at::Tensor& x, bool per_instance, doubl
                                    const c10::optional<at::Tensor>& running_mean,
                                    const c10::optional<at::Tensor>& running_var,
                                    const c10::optional<at::Tensor>& num_batches,
-                                   double momentum);
+                                   double momentum, int64_t up);
+std::vector<at::Tensor> norm_affine_fold(const at::Tensor& mean, const at::Tensor& rstd,
+                                         const c10::optional<at::Tensor>& weight,
+                                         const c10::optional<at::Tensor>& bias,
+                                         const c10::optional<at::Tensor>& count,
+                                         const c10::optional<at::Tensor>& var,
+                                         const c10::optional<at::Tensor>& running_mean,
+                                         const c10::optional<at::Tensor>& running_var,
+                                         const c10::optional<at::Tensor>& num_batches,
+                                         double momentum);
+std::vector<at::Tensor> norm_apply_pair(const at::Tensor& x, const at::Tensor& scale0,
+                                        const at::Tensor& shift0, const at::Tensor& scales,
+                                        const at::Tensor& shifts, const at::Tensor& gb0,
+                                        const at::Tensor& gbs, double slope0, double slopes,
+                                        int64_t up);
+at::Tensor norm_bwd_reduce_pair(const at::Tensor& x, const at::Tensor& dout0,
+                                const at::Tensor& douts, const at::Tensor& scale0,
+                                const at::Tensor& shift0, const at::Tensor& scales,
+                                const at::Tensor& shifts, const at::Tensor& mean0,
+                                const at::Tensor& rstd0, const at::Tensor& means,
+                                const at::Tensor& rstds, const at::Tensor& gb0,
+                                const at::Tensor& gbs, const at::Tensor& dgb0,
+                                const at::Tensor& dgbs, double slope0, double slopes,
+                                int64_t up);
+at::Tensor norm_bwd_apply_pair(const at::Tensor& x, const at::Tensor& dout0,
+                               const at::Tensor& douts, const at::Tensor& scale0,
+                               const at::Tensor& shift0, const at::Tensor& scales,
+                               const at::Tensor& shifts, const at::Tensor& mean,
+                               const at::Tensor& rstd, const std::vector<at::Tensor>& k0,
+                               const std::vector<at::Tensor>& ks, const at::Tensor& gb0,
+                               const at::Tensor& gbs, double slope0, double slopes, int64_t up);
 py::dict norm_plan(const at::Tensor& x, bool per_instance);
 std::vector<at::Tensor> sync_stats_merge(const at::Tensor& allst, double eps,
                                          const c10::optional<at::Tensor>& weight,
@@ -24,7 +54,8 @@ std::vector<at::Tensor> norm_bwd_coeffs(const at::Tensor& S1, const at::Tensor& 
                                         const at::Tensor& rstd,
                                         const c10::optional<at::Tensor>& weight,
                                         bool per_instance, double invM, bool need_dw,
-                                        bool need_db);
+                                        bool need_db, const c10::optional<at::Tensor>& S3,
+                                        const c10::optional<at::Tensor>& S4);
 at::Tensor norm_apply(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,
                       const c10::optional<at::Tensor>& gamma,
                       const c10::optional<at::Tensor>& beta, double slope);
@@ -34,7 +65,8 @@ std::vector<at::Tensor> norm_bwd_reduce(const at::Tensor& x, const at::Tensor& d
                                         const c10::optional<at::Tensor>& gamma,
                                         const c10::optional<at::Tensor>& beta,
                                         const c10::optional<at::Tensor>& dgamma,
-                                        const c10::optional<at::Tensor>& dbeta, double slope);
+                                        const c10::optional<at::Tensor>& dbeta, double slope,
+                                        bool bias_sums);
 at::Tensor norm_bwd_apply(const at::Tensor& x, const at::Tensor& dout, const at::Tensor& scale,
                           const at::Tensor& shift, const at::Tensor& mean, const at::Tensor& rstd,
                           const at::Tensor& k1, const at::Tensor& k2, const at::Tensor& k3,
@@ -358,14 +390,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("per_instance"), py::arg("eps"), py::arg("weight"),
         py::arg("bias"), py::arg("partial_only"), py::arg("running_mean") = py::none(),
         py::arg("running_var") = py::none(), py::arg("num_batches") = py::none(),
-        py::arg("momentum") = 0.0);
+        py::arg("momentum") = 0.0, py::arg("up") = 1);
+  m.def("norm_affine_fold", &iamd::norm_affine_fold,
+        "scale / shift of an affine over given statistics, + running statistics update (k1)",
+        py::arg("mean"), py::arg("rstd"), py::arg("weight") = py::none(),
+        py::arg("bias") = py::none(), py::arg("count") = py::none(), py::arg("var") = py::none(),
+        py::arg("running_mean") = py::none(), py::arg("running_var") = py::none(),
+        py::arg("num_batches") = py::none(), py::arg("momentum") = 0.0);
+  m.def("norm_apply_pair", &iamd::norm_apply_pair,
+        "two SPADE modulations + activations of one (nearest-upsampled) normalised x (k1)");
+  m.def("norm_bwd_reduce_pair", &iamd::norm_bwd_reduce_pair,
+        "k1 backward reduction of the pair: dgamma|dbeta maps and the [8, N, C] sums");
+  m.def("norm_bwd_apply_pair", &iamd::norm_bwd_apply_pair,
+        "k1 backward dx of the pair, summed onto the pre-upsample x");
   m.def("norm_plan", &iamd::norm_plan,
         "host-side plan of norm_stats / norm_bwd_reduce for x (launches nothing): cl, vec, tpr, "
         "rpb, nzc, chunk, P, rs_stats, rs_bwd",
         py::arg("x"), py::arg("per_instance"));
-  m.def("norm_bwd_coeffs", &iamd::norm_bwd_coeffs, "k1 backward coefficients from the sums");
+  m.def("norm_bwd_coeffs", &iamd::norm_bwd_coeffs,
+        "k1 backward coefficients from the sums (+ the [2C] gamma|beta conv bias gradient)",
+        py::arg("S1"), py::arg("S2"), py::arg("rstd"), py::arg("weight"),
+        py::arg("per_instance"), py::arg("invM"), py::arg("need_dw"), py::arg("need_db"),
+        py::arg("S3") = py::none(), py::arg("S4") = py::none());
   m.def("norm_apply", &iamd::norm_apply, "norm + SPADE modulation + activation (k1 fwd)");
-  m.def("norm_bwd_reduce", &iamd::norm_bwd_reduce, "k1 backward reduction");
+  m.def("norm_bwd_reduce", &iamd::norm_bwd_reduce, "k1 backward reduction", py::arg("x"),
+        py::arg("dout"), py::arg("scale"), py::arg("shift"), py::arg("mean"), py::arg("rstd"),
+        py::arg("gamma"), py::arg("beta"), py::arg("dgamma"), py::arg("dbeta"), py::arg("slope"),
+        py::arg("bias_sums") = false);
   m.def("norm_bwd_apply", &iamd::norm_bwd_apply, "k1 backward dx");
   m.def("bias_act_fwd", &iamd::bias_act_fwd, "bias + activation epilogue (k2)");
   m.def("bias_act_bwd", &iamd::bias_act_bwd, "k2 backward: dx and dbias");

@@ -288,16 +288,15 @@ class SPADEGenerator(nn.Module):
         x = self.cbn_head_0(x, z) if self.use_style_encoder else self.conv_head_0(x)
         x = self.head_1(x, seg)
         x = self.head_2(x, seg)
-        x = self.nearest_upsample2x(x)
-        x = self.up_0a(x, seg)
+        # (the 'a' blocks take the map before its upsampling: their two leading SPADE norms
+        # read it as a pair, layers/residual.py, and no upsampled copy is made)
+        x = self.up_0a(x, seg, pre_upsample=2)
         x = self.cbn_up_0a(x, z) if self.use_style_encoder else self.conv_up_0a(x)
         x = self.up_0b(x, seg)
-        x = self.nearest_upsample2x(x)
-        x = self.up_1a(x, seg)
+        x = self.up_1a(x, seg, pre_upsample=2)
         x = self.cbn_up_1a(x, z) if self.use_style_encoder else self.conv_up_1a(x)
         x = self.up_1b(x, seg)
-        x = self.nearest_upsample2x(x)
-        x = self.up_2a(x, seg)
+        x = self.up_2a(x, seg, pre_upsample=2)
         x = self.cbn_up_2a(x, z) if self.use_style_encoder else self.conv_up_2a(x)
         x = self.up_2b(x, seg)
         if self.out_image_small_side_size == 256 and x.is_cuda and \

@@ -24,7 +24,10 @@ from imaginaire_amd.ops import conv as nhwc_conv
 from torch import nn
 from torch.nn import functional as F
 
-from imaginaire_amd.ops.norm import defer_sync_bwd, fused_norm_act, prefetch_sync_stats
+from imaginaire_amd.ops import _ext
+from imaginaire_amd.ops.norm import (BiasGradHolder, _NormCfg, defer_sync_bwd, fused_norm_act,
+                                     fused_norm_act_pair, prefetch_sync_stats,
+                                     spade_pair_enabled, sync_active)
 from imaginaire_amd.ops.resize import interpolate
 from .conv import LinearBlock, Conv2dBlock, HyperConv2d, PartialConv2dBlock
 from .misc import PartialSequential
@@ -243,7 +246,8 @@ class _FusedNormBase(nn.Module):
     def _effective_mode(self):
         return self.mode
 
-    def fused(self, x, gamma=None, beta=None, gb=None, act_slope=1.0, deferred=None):
+    def fused(self, x, gamma=None, beta=None, gb=None, act_slope=1.0, deferred=None,
+              bias_grad=None):
         squeeze = None
         if x.dim() == 2:
             squeeze = x.shape
@@ -261,7 +265,7 @@ class _FusedNormBase(nn.Module):
             running_var=self.running_var if self.track_running_stats else None,
             training=use_batch, momentum=self._factor(True) if use_batch else 0.0, eps=self.eps,
             slope=act_slope, process_group=self.process_group, deferred=deferred,
-            num_batches=self._deferred_count(use_batch))
+            num_batches=self._deferred_count(use_batch), bias_grad=bias_grad)
         if squeeze is not None:
             y = y.reshape(squeeze)
         return y
@@ -312,13 +316,16 @@ class InstanceNorm2d(_FusedNormBase):
         super().__init__(num_features, eps, momentum, affine, track_running_stats)
 
 
-def fused_norm_or_none(norm, x, gamma=None, beta=None, gb=None, act_slope=1.0, deferred=None):
-    """Apply ``norm`` (fused module, torch module or None) + modulation + activation."""
+def fused_norm_or_none(norm, x, gamma=None, beta=None, gb=None, act_slope=1.0, deferred=None,
+                       bias_grad=None):
+    """Apply ``norm`` (fused module, torch module or None) + modulation + activation.
+    ``bias_grad``: the :class:`BiasGradHolder` shared with the conv that produced ``gb``."""
     if norm is None:
-        return fused_norm_act(x, 'none', gamma=gamma, beta=beta, gb=gb, slope=act_slope)
+        return fused_norm_act(x, 'none', gamma=gamma, beta=beta, gb=gb, slope=act_slope,
+                              bias_grad=bias_grad)
     if isinstance(norm, _FusedNormBase):
         return norm.fused(x, gamma=gamma, beta=beta, gb=gb, act_slope=act_slope,
-                          deferred=deferred)
+                          deferred=deferred, bias_grad=bias_grad)
     y = norm(x)
     if gb is not None:
         gamma, beta = gb.chunk(2, dim=1)
@@ -496,8 +503,9 @@ class SpatiallyAdaptiveNorm(nn.Module):
             return self.mlps[i][0](label_map)
         return cache.hidden(self, i, label_map)
 
-    def _gb(self, i, label_map):
-        """γ|β for condition i as one [N, 2C, H, W] tensor (first C = γ)."""
+    def _gb(self, i, label_map, bias_grad=None):
+        """γ|β for condition i as one [N, 2C, H, W] tensor (first C = γ). ``bias_grad``: the
+        holder in which the norm's backward leaves the γ|β conv's bias gradient."""
         if self.separate_projection:
             from .weight_norm import get_weight
             hidden = self._hidden(i, label_map) if len(self.mlps[i]) == 1 else \
@@ -507,7 +515,7 @@ class SpatiallyAdaptiveNorm(nn.Module):
             w = cat0(get_weight(cg), get_weight(cb))
             b = torch.cat([cg.bias, cb.bias], 0) if cg.bias is not None else None
             return nhwc_conv.conv2d(hidden, w, b, cg.stride, cg.padding, cg.dilation, cg.groups,
-                                    cg.padding_mode)
+                                    cg.padding_mode, bias_grad=bias_grad if b is not None else None)
         if len(self.mlps[i]) == 2 and not self.partial[i]:
             return self.mlps[i][1](self._hidden(i, label_map))
         return self.mlps[i](label_map)
@@ -526,19 +534,78 @@ class SpatiallyAdaptiveNorm(nn.Module):
                 # backward mirror: the norm's Σg, Σg·x̂ all-reduce runs while the γ|β / mlp
                 # convolution backward runs; this join node (created before them) finishes dx
                 x, deferred = defer_sync_bwd(x)
+        # the first condition's γ|β goes to the norm alone: its backward sums dγ|dβ per channel
+        # for the γ|β conv's bias gradient while it writes them (no second pass over the map)
+        holder = BiasGradHolder() if active and self.separate_projection else None
         gbs = []
         for i in active:
             label_map = LabelMapCache.resize(cond_inputs[i], size,
                                              conv_pad=not self.partial[i])
-            gbs.append(self._gb(i, label_map))
+            gbs.append(self._gb(i, label_map, holder if i == active[0] else None))
         if len(gbs) == 0:
             return fused_norm_or_none(self.norm, x, act_slope=act_slope)
         if len(gbs) == 1:
             return fused_norm_or_none(self.norm, x, gb=gbs[0], act_slope=act_slope,
-                                      deferred=deferred)
+                                      deferred=deferred, bias_grad=holder)
         return _modulate_more(fused_norm_or_none(self.norm, x, gb=gbs[0], act_slope=1.0,
-                                                 deferred=deferred),
+                                                 deferred=deferred, bias_grad=holder),
                               gbs[1:], act_slope)
+
+
+    def pair_applies(self, other, x_low, cond_inputs):
+        """``self`` and ``other`` can normalise the nearest upsampling of ``x_low`` as a pair
+        (:meth:`forward_pair`): two SPADE layers with one active, non-partial condition over
+        the same kind of batch norm (param-free or with its per-channel affine; same eps and
+        momentum, no cross-rank exchange active), on a packed channels-last GPU tensor with
+        C % 8 == 0. This decides for the modules; what the kernels themselves need of the
+        tensors (ops/norm.py ``pair_native_ok``, which sees the γ|β maps as well) is checked
+        again there and falls back to upsample + two norms by itself."""
+        if not (spade_pair_enabled() and type(other) is SpatiallyAdaptiveNorm and
+                type(self) is SpatiallyAdaptiveNorm):
+            return False
+        active = [i for i in range(len(cond_inputs)) if cond_inputs[i] is not None]
+        if len(active) != 1 or active[0] >= len(self.mlps) or active[0] >= len(other.mlps) or \
+                self.partial[active[0]] or other.partial[active[0]] or \
+                self.num_features != other.num_features:
+            return False
+        a, b = self.norm, other.norm
+        if not (isinstance(a, _FusedNormBase) and type(a) is type(b) and
+                type(a) in (BatchNorm2d, SyncBatchNorm) and a.affine == b.affine and
+                a.eps == b.eps and a.momentum == b.momentum and a.momentum is not None and
+                a.track_running_stats == b.track_running_stats and a.training == b.training and
+                a.process_group is b.process_group and a._effective_mode() == 'batch' and
+                not sync_active(a.process_group)):
+            return False
+        return torch.is_tensor(x_low) and x_low.dim() == 4 and _ext.use_native(x_low) and \
+            x_low.dtype in (torch.bfloat16, torch.float32) and x_low.shape[1] % 8 == 0 and \
+            x_low.shape[1] == self.num_features and x_low.numel() > 0 and \
+            x_low.is_contiguous(memory_format=torch.channels_last)
+
+    def forward_pair(self, other, x_low, up, *cond_inputs, act_slopes=(1.0, 1.0)):
+        """``(self(x), other(x))`` for ``x`` the nearest upsampling of ``x_low`` by ``up``, which
+        is never materialised (ops/norm.py ``fused_norm_act_pair``). The caller checked
+        :meth:`pair_applies`. Both γ|β maps are computed at the upsampled size, in the order
+        the two layers would ask for them. Neither layer's ``forward`` nor its norm module is
+        called, so forward hooks registered on them do not fire on this path
+        (``IMAGINAIRE_AMD_SPADE_PAIR=0`` when they must)."""
+        i = [k for k in range(len(cond_inputs)) if cond_inputs[k] is not None][0]
+        size = (x_low.shape[2] * up, x_low.shape[3] * up)
+        gbs, holders, running, affines = [], [], [], []
+        norm = self.norm
+        use_batch = norm.training or not norm.track_running_stats
+        for layer in (self, other):
+            label_map = LabelMapCache.resize(cond_inputs[i], size, conv_pad=True)
+            holders.append(BiasGradHolder() if layer.separate_projection else None)
+            gbs.append(layer._gb(i, label_map, holders[-1]))
+            n = layer.norm
+            running.append((n.running_mean if n.track_running_stats else None,
+                            n.running_var if n.track_running_stats else None,
+                            n._deferred_count(use_batch)))
+            affines.append((n.weight, n.bias))
+        cfg = _NormCfg('batch', use_batch, norm._factor(True) if use_batch else 0.0, norm.eps,
+                       1.0, norm.process_group)
+        return fused_norm_act_pair(x_low, up, gbs[0], gbs[1], act_slopes, cfg, holders, running,
+                                   affines)
 
 
 class HyperSpatiallyAdaptiveNorm(nn.Module):

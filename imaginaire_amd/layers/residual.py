@@ -93,7 +93,49 @@ class _BaseResBlock(nn.Module):
             self._fuse_ok = ok
         return ok
 
-    def forward(self, x, *cond_inputs, do_checkpoint=False, **kw_cond_inputs):
+    def _pair_norms(self, x, cond_inputs, kw_cond_inputs, do_checkpoint):
+        """``(norm_0, norm_s, slope_0, slope_s)`` when the block's two leading SPADE norms can
+        run as a pair on the not yet upsampled ``x`` (activation_norm.py ``pair_applies``):
+        a learned shortcut on the fused-shortcut path, conv_block_0 and conv_block_s both
+        'N[A]C' blocks over SPADE layers. Else None."""
+        from .activation_norm import SpatiallyAdaptiveNorm
+        from .nonlinearity import act_slope
+        if do_checkpoint or kw_cond_inputs or not self.learn_shortcut or \
+                not self._fused_shortcut_ok():
+            return None
+        found = []
+        for blk in (self.conv_block_0, self.conv_block_s):
+            if type(blk).forward is not _BaseConvBlock.forward:
+                return None
+            keys = list(blk.layers.keys())
+            if keys not in (['norm', 'nonlinearity', 'conv'], ['norm', 'conv']) or \
+                    type(blk.layers['norm']) is not SpatiallyAdaptiveNorm:
+                return None
+            slope = act_slope(blk.layers['nonlinearity']) if len(keys) == 3 else 1.0
+            if slope is None:
+                return None
+            found.append((blk.layers['norm'], slope))
+        (n0, s0), (ns, ss) = found
+        if not n0.pair_applies(ns, x, cond_inputs):
+            return None
+        return n0, ns, s0, ss
+
+    def forward(self, x, *cond_inputs, do_checkpoint=False, pre_upsample=None,
+                **kw_cond_inputs):
+        """``pre_upsample``: the block's input is the nearest upsampling of ``x`` by this
+        factor. Where the two leading SPADE norms can read ``x`` itself (:meth:`_pair_norms`)
+        no upsampled copy is made; otherwise it is upsampled here."""
+        if pre_upsample:
+            pair = self._pair_norms(x, cond_inputs, kw_cond_inputs, do_checkpoint)
+            if pair is not None:
+                n0, ns, s0, ss = pair
+                y0, ys = n0.forward_pair(ns, x, int(pre_upsample), *cond_inputs,
+                                         act_slopes=(s0, ss))
+                dx = self.conv_block_0(y0, *cond_inputs, normed_input=True)
+                x_shortcut = self.conv_block_s(ys, *cond_inputs, normed_input=True)
+                return self.conv_block_1(dx, *cond_inputs, residual=x_shortcut)
+            from imaginaire_amd.ops.resize import interpolate
+            x = interpolate(x, scale_factor=float(pre_upsample), mode='nearest')
         if not do_checkpoint and self._fused_shortcut_ok():
             # x_shortcut + dx with the add in the epilogue of the branch's last conv (k10) when
             # the branch ends in one (pre-activation 'NACNAC' blocks of SPADE / FUNIT / the

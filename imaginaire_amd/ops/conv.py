@@ -36,6 +36,7 @@ Reference: the reference's blocks call cuDNN through ``nn.Conv2d`` (layers/conv.
 import collections
 import contextlib
 import os
+import threading
 
 import torch
 import torch.nn.functional as F
@@ -503,6 +504,25 @@ def _bias_grad(t):
     return _ext.ext().bias_act_bwd(t, t, 1.0)[1]
 
 
+class _HeldBiasGrad(threading.local):
+    """conv2d(bias_grad=) on its way through _run into _MfmaConv2d.forward of the SAME call,
+    per thread. It does not ride in the Function's arguments because their count is part of the
+    recorded backward route table (tests/data/conv_routes.json holds every backward's return
+    tuple), which a change like this one must leave as it is."""
+    holder = None
+
+
+_HELD_BIAS_GRAD = _HeldBiasGrad()
+
+
+def _held_bias_grad(holder, dy, operand):
+    """The bias gradient at the identity activation: the channel sums the producer of ``dy``
+    left in ``holder`` (a SPADE norm's backward, ops/norm.py BiasGradHolder) when they are sums
+    over this very ``dy``, else the k2 pass over ``operand``."""
+    db = holder.take(dy) if holder is not None else None
+    return db if db is not None else _bias_grad(operand)
+
+
 def _finish_grads(dw, db, cout, cin, wdt, bdt, need_b):
     """The tail of the k10 backwards: (dw, db) cropped to the real channels and cast to the
     parameters' dtypes; every weight gradient passes the ``_TEST_FLIP_WGRAD`` hook here."""
@@ -673,6 +693,9 @@ class _MfmaConv2d(torch.autograd.Function):
         # themselves (the conv of F.pad(x, mode) at padding 0, no padded copy made or saved)
         cout, cin = w.shape[0], w.shape[1]
         assert not pmode or cout > 16, 'thin-output convs keep the explicit pad'
+        # the holder the output's consumer may leave the bias gradient in (conv2d hands it over
+        # beside the arguments: the Function's signature is part of the recorded route table)
+        ctx.bias_grad, _HELD_BIAS_GRAD.holder = _HELD_BIAS_GRAD.holder, None
         cp, op = _round_up(cin, 64), _out_pad(cout)
         xb = _pad_channels(x, cp, torch.bfloat16)
         sig = None if sw is None else sw.sigma.reshape(1)
@@ -739,7 +762,7 @@ class _MfmaConv2d(torch.autograd.Function):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 if r.db == 'side':
-                    db = _bias_grad(dy)
+                    db = _held_bias_grad(ctx.bias_grad, dy_in, dy)
                 if r.side_w:  # QUIRK: no dest here: this one does not go into the DDP bucket
                     dw = _wgrad(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn,
                                 pmode=pmode)
@@ -765,7 +788,7 @@ class _MfmaConv2d(torch.autograd.Function):
             dw = _wgrad(dy, xb, wb, stride, padding, dilation, cout, cin, wdt, sn, dest,
                         pmode=pmode)
         if r.db == 'last':  # after the data and weight gradients
-            db = _bias_grad(dy_b)
+            db = _held_bias_grad(ctx.bias_grad, dy_in, dy_b)
         dw, db = _finish_grads(dw, db, cout, cin, wdt, bdt, need_b)
         if _PS_CHECK:
             for nm, t in (('conv.db', db), ('conv.dw', dw), ('conv.dx', dx)):
@@ -1660,12 +1683,21 @@ def _miopen_conv2d(x, weight, bias, stride, padding, dilation, groups, cpad):
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1,
-           padding_mode='zeros', residual=None):
+           padding_mode='zeros', residual=None, bias_grad=None):
     """``F.conv2d`` (+ ``residual``, added to the output: on the k10 path inside its epilogue,
-    otherwise as a separate add). ``weight`` may be an :class:`SNWeight`."""
+    otherwise as a separate add). ``weight`` may be an :class:`SNWeight`. ``bias_grad``: a holder
+    (ops/norm.py ``BiasGradHolder``) in which the output's only consumer may leave the channel
+    sums of the output's gradient during its backward; the k10 backward then takes them as the
+    bias gradient instead of summing that gradient again. Empty or unmatched: it sums."""
     st, pd, dl = _pair(stride), _pair(padding), _pair(dilation)
-    return _run(_route(x, weight, st, pd, dl, groups, padding_mode, residual), x, weight, bias,
-                st, pd, dl, groups, padding_mode, residual, 1.0)
+    r = _route(x, weight, st, pd, dl, groups, padding_mode, residual)
+    if bias_grad is None or r.kind != 'k10':
+        return _run(r, x, weight, bias, st, pd, dl, groups, padding_mode, residual, 1.0)
+    _HELD_BIAS_GRAD.holder = bias_grad  # taken by this call's k10 Function's forward
+    try:
+        return _run(r, x, weight, bias, st, pd, dl, groups, padding_mode, residual, 1.0)
+    finally:
+        _HELD_BIAS_GRAD.holder = None
 
 
 def conv2d_act(x, weight, bias=None, stride=1, padding=0, dilation=1, slope=1.0):

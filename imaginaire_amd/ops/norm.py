@@ -194,11 +194,12 @@ def _expand_mod(t, x):
 
 class _NormCfg:
     __slots__ = ('mode', 'training', 'momentum', 'eps', 'slope', 'group', 'use_batch_stats',
-                 'deferred', 'num_batches')
+                 'deferred', 'num_batches', 'bias_grad')
 
     def __init__(self, mode, training, momentum, eps, slope, group, deferred=None,
-                 num_batches=None):
+                 num_batches=None, bias_grad=None):
         self.num_batches = num_batches
+        self.bias_grad = bias_grad
         self.mode = mode
         self.training = training
         self.momentum = momentum
@@ -270,6 +271,41 @@ def defer_sync_bwd(x):
     if st is not None:  # the prefetched statistics exchange belongs to the same values
         x1._iamd_bn_stats = st
     return x1, holder
+
+
+# ---- bias gradient of the γ|β convolution --------------------------------------------------
+# The γ|β conv's bias gradient is the per-channel sum of the dγ|dβ map the norm's backward
+# writes. The reduce kernel has those values in registers, so it sums them (after rounding to
+# the stored dtype: the very numbers the conv's own bias pass would read back) and the conv's
+# backward, which runs next, takes the [2C] vector instead of re-reading the map.
+
+class BiasGradHolder(object):
+    """Hand-off of Σdγ|Σdβ (fp32 [2C], γ half first) between a SPADE norm's backward and the
+    backward of the γ|β convolution that produced its ``gb``."""
+    __slots__ = ('db', 'src', 'ver')
+    filled = 0  # holders a norm backward filled / a conv backward used (tests / diagnostics)
+    used = 0
+
+    def __init__(self):
+        self.db = self.src = self.ver = None
+
+    def fill(self, db, dgb):
+        """``db``: the channel sums of ``dgb``, the gradient the norm's backward returns."""
+        self.db, self.src, self.ver = db, dgb, dgb._version
+        BiasGradHolder.filled += 1
+
+    def take(self, dy):
+        """The sums if ``dy`` is the very tensor they were taken over (unchanged since), else
+        None: the conv then sums its bias gradient itself. Empties the holder."""
+        db, src, ver = self.db, self.src, self.ver
+        self.db = self.src = self.ver = None
+        if db is None or dy is None or dy.data_ptr() != src.data_ptr() or \
+                dy.shape != src.shape or dy.stride() != src.stride() or \
+                dy.dtype != src.dtype or dy._version != ver or \
+                db.numel() != dy.shape[1]:
+            return None
+        BiasGradHolder.used += 1
+        return db
 
 
 class _FusedNormActFn(torch.autograd.Function):
@@ -385,9 +421,13 @@ class _FusedNormActFn(torch.autograd.Function):
                 dbet_v = torch.empty_like(beta_v, memory_format=fmt)
         else:
             gamma_v = beta_v = dgam_v = dbet_v = None
+        # Σdγ, Σdβ for the γ|β conv's bias gradient, summed by the same pass (BiasGradHolder)
+        holder = cfg.bias_grad if ctx.has_gb else None
         sums = ext.norm_bwd_reduce(x, dout, scale, shift, mean, rstd, gamma_v, beta_v,
-                                   dgam_v, dbet_v, cfg.slope)
+                                   dgam_v, dbet_v, cfg.slope, holder is not None)
         S1, S2 = sums[0], sums[1]
+        if holder is not None and len(sums) != 4:
+            holder = None
         if ctx.has_mod and ctx.mod_bcast:
             dgamma = sums[2].to(ctx.mod_dtypes[0])
             dbeta = sums[3].to(ctx.mod_dtypes[1])
@@ -402,15 +442,20 @@ class _FusedNormActFn(torch.autograd.Function):
                 S1.dtype == torch.float32 and S1.is_contiguous() and S2.is_contiguous():
             # one launch for k1 / k2 / k3 and the affine gradients
             inst = cfg.mode == 'instance'
-            k1, k2, k3, dw32, db32 = ext.norm_bwd_coeffs(
+            k1, k2, k3, dw32, db32, bsum = ext.norm_bwd_coeffs(
                 S1, S2, rstd.contiguous(), weight, inst, 1.0 / float(HW if inst else N * HW),
-                need_dw, need_db)
+                need_dw, need_db, sums[2] if holder is not None else None,
+                sums[3] if holder is not None else None)
+            if holder is not None:
+                holder.fill(bsum, dgb)
             dweight = dw32.to(weight.dtype) if need_dw else None
             dbias = db32.to(weight.dtype if weight is not None else torch.float32) \
                 if need_db else None
             dx = ext.norm_bwd_apply(x, dout, scale, shift, mean, rstd, k1, k2, k3, gamma_v,
                                     beta_v, cfg.slope) if ctx.needs_input_grad[0] else None
             return dx, dweight, dbias, dgamma, dbeta, dgb, None, None, None
+        if holder is not None:
+            holder.fill(torch.cat([sums[2].sum(0), sums[3].sum(0)]), dgb)
         batch_sums = cfg.mode not in ('none', 'instance') and cfg.use_batch_stats
         s_loc = None
         if need_dw or need_db or batch_sums:
@@ -453,6 +498,167 @@ class _FusedNormActFn(torch.autograd.Function):
         dx = ext.norm_bwd_apply(x, dout, scale, shift, mean_b, rstd_b, k1, k2, k3,
                                 gamma_v, beta_v, cfg.slope) if ctx.needs_input_grad[0] else None
         return dx, dweight, dbias, dgamma, dbeta, dgb, None, None, None
+
+
+# ---- two SPADE norms of one (upsampled) tensor --------------------------------------------
+# The first residual block after each upsampling of the SPADE generator normalises the SAME
+# nearest-upsampled tensor twice (conv_block_0's norm and the learned shortcut's), each with
+# its own γ|β map. The pair op takes the tensor BEFORE the upsampling: statistics, forward and
+# both backward passes read each low-resolution value once instead of its up² copies per
+# norm, no upsampled copy is written or saved, and the two data gradients, their fan-in add
+# and the upsampling's backward collapse into the one dx the last kernel stores.
+# IMAGINAIRE_AMD_SPADE_PAIR=0: upsample, then the two norms one by one (A/B reference).
+
+def spade_pair_enabled():
+    return os.environ.get('IMAGINAIRE_AMD_SPADE_PAIR', '1') != '0'
+
+
+class _FusedNormActPairFn(torch.autograd.Function):
+    """HIP path of :func:`fused_norm_act_pair` (batch norm, channels-last). ``w0, b0`` /
+    ``ws, bs``: each norm's per-channel affine (or None)."""
+    launches = 0  # forward launches of the pair kernel (tests / diagnostics)
+
+    @staticmethod
+    def forward(ctx, x, gb0, gbs, w0, b0, ws, bs, cfg, up, slopes, running, holders):
+        ext = _ext.ext()
+        C = x.shape[1]
+        (rm0, rv0, nb0), (rms, rvs, nbs) = running
+        w0f, b0f, wsf, bsf = [None if t is None else t.float() for t in (w0, b0, ws, bs)]
+        if cfg.use_batch_stats:
+            # the statistics of the upsampled tensor, bit for bit, read from the low-resolution
+            # one, once for both norms; the same kernels fold each norm's affine and update its
+            # running statistics and batch counter in place
+            fold0 = cfg.training and _native_running(rm0, rv0, cfg) and \
+                (nb0 is None or nb0.dtype == torch.int64)
+            folds = cfg.training and _native_running(rms, rvs, cfg) and \
+                (nbs is None or nbs.dtype == torch.int64)
+            count, mean0, var, scale0, shift0, rstd0 = ext.norm_stats(
+                x, False, cfg.eps, w0f, b0f, False, rm0 if fold0 else None,
+                rv0 if fold0 else None, nb0 if fold0 else None, float(cfg.momentum), up)
+            scales, shifts = ext.norm_affine_fold(
+                mean0, rstd0, wsf, bsf, count, var, rms if folds else None,
+                rvs if folds else None, nbs if folds else None, float(cfg.momentum))
+            means, rstds = mean0, rstd0
+            if cfg.training:
+                for fold, rm, rv, nb in ((fold0, rm0, rv0, nb0), (folds, rms, rvs, nbs)):
+                    if not fold:
+                        _update_running(rm, rv, mean0, var, count, cfg.momentum)
+                        if nb is not None:
+                            nb.add_(1)
+        else:  # eval: each norm's own running statistics, no batch terms in the backward
+            st = []
+            for rm, rv, w, b in ((rm0, rv0, w0f, b0f), (rms, rvs, wsf, bsf)):
+                mean = rm.float().reshape(1, C).contiguous()
+                rstd = torch.rsqrt(rv.float().reshape(1, C) + cfg.eps)
+                sc = (rstd * (w.reshape(1, C) if w is not None else 1.0)).contiguous()
+                sh = ((b.reshape(1, C) if b is not None else 0.0) - mean * sc).contiguous()
+                st += [sc, sh, mean, rstd]
+            scale0, shift0, mean0, rstd0, scales, shifts, means, rstds = st
+        out0, outs = ext.norm_apply_pair(x, scale0, shift0, scales, shifts, gb0, gbs, slopes[0],
+                                         slopes[1], up)
+        _FusedNormActPairFn.launches += 1
+        ctx.cfg, ctx.up, ctx.slopes, ctx.holders = cfg, up, slopes, holders
+        ctx.save_for_backward(x, gb0, gbs, w0, b0, ws, bs, scale0, shift0, scales, shifts,
+                              mean0, rstd0, means, rstds)
+        return out0, outs
+
+    @staticmethod
+    def backward(ctx, dout0, douts):
+        x, gb0, gbs, w0, b0, ws, bs, scale0, shift0, scales, shifts, mean0, rstd0, means, \
+            rstds = ctx.saved_tensors
+        cfg, up, slopes = ctx.cfg, ctx.up, ctx.slopes
+        ext = _ext.ext()
+        N, C, H, W = gb0.shape[0], x.shape[1], gb0.shape[2], gb0.shape[3]
+        cl = torch.channels_last
+
+        def grad(d):
+            if d is None:
+                return x.new_zeros((N, C, H, W)).contiguous(memory_format=cl)
+            return d.to(x.dtype).contiguous(memory_format=cl)
+
+        dout0, douts = grad(dout0), grad(douts)
+        dgb0, dgbs = torch.empty_like(gb0), torch.empty_like(gbs)
+        sums = ext.norm_bwd_reduce_pair(x, dout0, douts, scale0, shift0, scales, shifts, mean0,
+                                        rstd0, means, rstds, gb0, gbs, dgb0, dgbs, slopes[0],
+                                        slopes[1], up)
+        ks, daff = [], []
+        for q, (holder, dgb, scale, w, b) in enumerate(zip(
+                ctx.holders, (dgb0, dgbs), (scale0, scales), (w0, ws), (b0, bs))):
+            S = sums[4 * q:4 * q + 4]
+            need_dw = w is not None and ctx.needs_input_grad[3 + 2 * q]
+            need_db = b is not None and ctx.needs_input_grad[4 + 2 * q]
+            if cfg.use_batch_stats:
+                # k1 / k2 / k3, the affine gradients and the γ|β conv's bias gradient: one launch
+                k1, k2, k3, dw, db, bsum = ext.norm_bwd_coeffs(
+                    S[0], S[1], rstd0, w, False, 1.0 / float(N * H * W), need_dw, need_db,
+                    S[2], S[3])
+            else:  # no batch statistics in the graph: dx = g * scale
+                k1 = scale
+                k2 = k3 = torch.zeros_like(k1)
+                dw = S[1].sum(0) if need_dw else None
+                db = S[0].sum(0) if need_db else None
+                bsum = torch.cat([S[2].sum(0), S[3].sum(0)]) if holder is not None else None
+            if holder is not None:
+                holder.fill(bsum, dgb)
+            ks.append([k1, k2, k3])
+            daff += [dw.to(w.dtype) if need_dw else None, db.to(b.dtype) if need_db else None]
+        dx = ext.norm_bwd_apply_pair(x, dout0, douts, scale0, shift0, scales, shifts, mean0,
+                                     rstd0, ks[0], ks[1], gb0, gbs, slopes[0], slopes[1], up) \
+            if ctx.needs_input_grad[0] else None
+        return (dx, dgb0, dgbs) + tuple(daff) + (None,) * 5
+
+
+def _upsample_nearest(x, up):
+    if up == 1:
+        return x
+    from imaginaire_amd.ops.resize import interpolate
+    return interpolate(x, scale_factor=float(up), mode='nearest')
+
+
+def pair_native_ok(x, up, gb0, gbs, cfg, affines=((None, None), (None, None))):
+    """The pair kernels can run: HIP path, packed channels-last bf16 / fp32 x with C % 8 == 0,
+    up 1 or 2, packed γ|β maps of x's dtype at the upsampled size, a batch norm without a
+    cross-rank exchange (its affine weight and bias both given or both absent), and the switch
+    on."""
+    if not (spade_pair_enabled() and up in (1, 2) and x.dim() == 4 and _ext.use_native(x) and
+            x.dtype in (torch.bfloat16, torch.float32) and x.shape[1] % 8 == 0 and
+            x.numel() > 0 and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    if cfg.mode not in ('batch', 'sync_batch') or \
+            (cfg.mode == 'sync_batch' and cfg.training and sync_active(cfg.group)):
+        return False
+    if any((w is None) != (b is None) or (w is not None and (not w.is_cuda or w.dim() != 1 or
+                                                              w.numel() != x.shape[1]))
+           for w, b in affines):
+        return False
+    shape = (x.shape[0], 2 * x.shape[1], x.shape[2] * up, x.shape[3] * up)
+    return all(g is not None and tuple(g.shape) == shape and g.dtype == x.dtype and g.is_cuda and
+               g.is_contiguous(memory_format=torch.channels_last) for g in (gb0, gbs))
+
+
+def fused_norm_act_pair(x_low, up, gb0, gbs, slopes, cfg, holders=(None, None),
+                        running=((None, None, None), (None, None, None)),
+                        affines=((None, None), (None, None))):
+    """``(out0, outs)``: the batch norm of ``nearest_upsample(x_low, up)`` under two SPADE
+    modulations ``gb0`` / ``gbs`` ([N, 2C, up·h, up·w], γ first) with activation slopes
+    ``slopes``. ``cfg``: the :class:`_NormCfg` both norms share; ``running``: each norm's
+    (running_mean, running_var, num_batches); ``affines``: each norm's (weight, bias) or
+    (None, None); ``holders``: each γ|β conv's :class:`BiasGradHolder` (or None). Off the
+    pair path (:func:`pair_native_ok`) this is the upsampling followed by two
+    :func:`fused_norm_act` calls."""
+    if pair_native_ok(x_low, up, gb0, gbs, cfg, affines):
+        (w0, b0), (ws, bs) = affines
+        return _FusedNormActPairFn.apply(x_low, gb0, gbs, w0, b0, ws, bs, cfg, up, tuple(slopes),
+                                         running, tuple(holders))
+    xu = _upsample_nearest(x_low, up)
+    outs = []
+    for gb, slope, holder, (rm, rv, nb), (w, b) in zip((gb0, gbs), slopes, holders, running,
+                                                       affines):
+        outs.append(fused_norm_act(
+            xu, cfg.mode, w, b, gb=gb, running_mean=rm, running_var=rv,
+            training=cfg.use_batch_stats, momentum=cfg.momentum, eps=cfg.eps, slope=slope,
+            process_group=cfg.group, num_batches=nb, bias_grad=holder))
+    return outs[0], outs[1]
 
 
 def _reference(x, mode, weight, bias, gamma, beta, gb, running_mean, running_var, cfg):
@@ -528,20 +734,23 @@ class _SyncStats(torch.autograd.Function):
 
 def fused_norm_act(x, mode='batch', weight=None, bias=None, gamma=None, beta=None, gb=None,
                    running_mean=None, running_var=None, training=True, momentum=0.1,
-                   eps=1e-5, slope=1.0, process_group=None, deferred=None, num_batches=None):
+                   eps=1e-5, slope=1.0, process_group=None, deferred=None, num_batches=None,
+                   bias_grad=None):
     """``act((norm(x)·w + b)·(1+γ) + β)`` — see module docstring.
 
     ``momentum`` is the already-resolved exponential-average factor. ``num_batches`` (the
     layer's ``num_batches_tracked``) is incremented when the running statistics are updated.
     ``gb`` is an alternative to (γ, β): one [N, 2C, H, W] tensor whose first C
-    channels are γ and last C are β (output of a fused γ|β convolution).
+    channels are γ and last C are β (output of a fused γ|β convolution). ``bias_grad`` (a
+    :class:`BiasGradHolder` the convolution that produced ``gb`` also holds) receives the
+    channel sums of ``gb``'s gradient from the backward on the HIP path.
     """
     if mode == 'sync_batch' and not training:
         mode_eff = 'batch'
     else:
         mode_eff = mode
     cfg = _NormCfg(mode_eff, training, momentum, eps, slope, process_group, deferred,
-                   num_batches)
+                   num_batches, bias_grad if gb is not None else None)
     if gamma is not None and gamma.dim() == 2 and x.shape[2] * x.shape[3] == 1:
         gamma = gamma.reshape(x.shape[0], x.shape[1], 1, 1)
         beta = beta.reshape(x.shape[0], x.shape[1], 1, 1)
