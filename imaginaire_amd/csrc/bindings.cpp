@@ -159,6 +159,12 @@ void splat_update(const at::Tensor& image, const at::Tensor& rows, const at::Ten
                   at::Tensor& win_pt);
 at::Tensor splat_render(const at::Tensor& rows, const at::Tensor& counts, const at::Tensor& color,
                         at::Tensor& counters, at::Tensor& win_px, int64_t h, int64_t w);
+// label.hip (k19 packed label maps -> one-hot | dense label tensor)
+at::Tensor label_expand(const c10::optional<at::Tensor>& idx,
+                        const c10::optional<at::Tensor>& dense, std::vector<int64_t> kind,
+                        std::vector<int64_t> cn, std::vector<int64_t> src, int64_t pad_to,
+                        int64_t Ho, int64_t Wo, double scale_h, double scale_w,
+                        at::ScalarType dtype, bool channels_last);
 // flow_warp.hip (k9 warp, k7 resample2d)
 at::Tensor flow_warp_fwd(const at::Tensor& img, const at::Tensor& flow);
 std::vector<at::Tensor> flow_warp_bwd(const at::Tensor& img, const at::Tensor& flow,
@@ -469,6 +475,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "colour the unseen listed points of a device point cloud from an image, in place (k18)");
   m.def("splat_render", &iamd::splat_render,
         "guidance image + seen mask [B, 4, h, w] of the listed points (k18)");
+  m.def("label_expand", &iamd::label_expand,
+        "index planes + dense channels -> label tensor, nearest resize and zero pad fused (k19)");
   m.def("flow_warp_fwd", &iamd::flow_warp_fwd, "bilinear flow warp, border (k9)");
   m.def("flow_warp_bwd", &iamd::flow_warp_bwd, "k9 backward", py::arg("img"), py::arg("flow"),
         py::arg("dout"), py::arg("need_dimg") = true);

@@ -17,18 +17,13 @@
 // src = scale * dst; otherwise src = max(scale * (dst + 0.5) - 0.5, 0)) with the caller's
 // scale, so results match F.interpolate bit-for-bit up to the output rounding.
 #include "common.h"
+#include "resize_index.h"
 
 namespace iamd {
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxTaps = 8;  // output rows (cols) a single input row (col) can feed
-
-struct Axis {
-  int in, out;
-  float scale;
-  bool ac;
-};
 
 __device__ __forceinline__ float src_index(const Axis& a, int dst) {
   if (a.ac) return a.scale * (float)dst;
@@ -151,14 +146,7 @@ resize_bwd(const T* __restrict__ dy, T* __restrict__ dx, int B, int C, Axis ay, 
   }
 }
 
-// ---- nearest (PyTorch's nearest_idx: exact 2x -> o >> 1, same size -> o, otherwise
-// min(floor(o * scale), in - 1) in float) --------------------------------------------------
-__device__ __forceinline__ int nearest_src(const Axis& a, int o) {
-  if (a.out == a.in) return o;
-  if (a.out == 2 * a.in) return o >> 1;
-  return min((int)floorf((float)o * a.scale), a.in - 1);
-}
-
+// ---- nearest: the source rule is nearest_src (resize_index.h) -------------------------------
 template <typename T>
 __global__ void __launch_bounds__(kThreads)
 nearest_fwd(const T* __restrict__ x, T* __restrict__ y, int B, int C, Axis ay, Axis ax) {
@@ -225,15 +213,6 @@ nearest_bwd(const T* __restrict__ dy, T* __restrict__ dx, int B, int C, Axis ay,
       }
     store_vec<T, 8>(dx + t * 8, acc);
   }
-}
-
-Axis make_axis(int64_t in, int64_t out, double scale, bool ac) {
-  Axis a;
-  a.in = (int)in;
-  a.out = (int)out;
-  a.scale = (float)scale;
-  a.ac = ac;
-  return a;
 }
 
 int grid_for(int64_t n) { return (int)std::min<int64_t>((n + kThreads - 1) / kThreads, 65536); }

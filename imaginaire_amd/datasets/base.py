@@ -4,7 +4,9 @@
 Per sample: load raw entries for every data type -> ``pre_aug_ops`` ->
 (paired / unpaired) replayed augmentation -> ``post_aug_ops`` ->
 ``full_data_post_aug_ops`` -> to tensor (+[-1, 1] normalisation) -> one-hot
-expansion of index label maps -> ``full_data_ops``. Op strings:
+expansion of index label maps -> ``full_data_ops``. With ``packed_labels: true`` the label
+types stay index planes instead (``make_packed_labels``; the trainer expands them on the
+device). Op strings:
 
 * ``to_tensor``, ``to_numpy``, ``decode_json`` (and ``decode_pkl``, which
   only runs when ``IMAGINAIRE_AMD_ALLOW_PICKLE=1`` because it unpickles data);
@@ -124,6 +126,8 @@ class BaseDataset(data.Dataset):
             self.full_data_post_aug_ops = [
                 op.strip() for op in self.cfgdata.full_data_post_aug_ops.split(',')]
         self.input_labels = list(getattr(self.cfgdata, 'input_labels', []))
+        # opt-in: one-hot label types travel as index planes (make_packed_labels)
+        self.packed_labels = bool(getattr(self.cfgdata, 'packed_labels', False))
         self.keypoint_data_types = list(getattr(self.cfgdata, 'keypoint_data_types', []))
         if is_test:
             aug_list = self.cfgdata.test.augmentations
@@ -212,25 +216,106 @@ class BaseDataset(data.Dataset):
                 imgs[idx] = _image_to_tensor(arr, self.normalize[data_type])
         return data
 
+    @staticmethod
+    def _encode_index(label_map, num_labels, dtype):
+        """The index plane ``_encode_onehot`` scatters from: ids in [0, num_labels], the last
+        one standing for "don't care / out of range"."""
+        label_map = label_map.clone()
+        label_map[label_map < 0] = num_labels
+        label_map[label_map >= num_labels] = num_labels
+        return label_map.long().to(dtype)
+
+    def _needs_one_hot(self, data_type, got):
+        """Whether tensors of ``data_type`` with ``got`` channels are index maps to expand."""
+        expected = self.num_channels[data_type]
+        if expected is None:
+            return False
+        if got < expected:
+            if got != 1:
+                raise ValueError('Num channels: %d. One-hot expansion can only be done if '
+                                 'image has 1 channel' % got)
+            assert str(self.interpolators[data_type]).upper() == NEAREST, \
+                'Cant do one-hot on image which has been resized with BILINEAR.'
+            return True
+        if got > expected:
+            raise ValueError('Data type: %s, Num channels %d > Expected num channels %d' %
+                             (data_type, got, expected))
+        return False
+
     def make_one_hot(self, data):
         for data_type in self.image_data_types:
-            expected = self.num_channels[data_type]
-            if expected is None:
-                continue
-            got = data[data_type][0].size(0)
-            if got < expected:
-                if got != 1:
-                    raise ValueError('Num channels: %d. One-hot expansion can only be done if '
-                                     'image has 1 channel' % got)
-                assert str(self.interpolators[data_type]).upper() == NEAREST, \
-                    'Cant do one-hot on image which has been resized with BILINEAR.'
+            if self._needs_one_hot(data_type, data[data_type][0].size(0)):
+                expected = self.num_channels[data_type]
                 udc = self.use_dont_care.get(data_type, False)
                 for idx in range(len(data[data_type])):
                     data[data_type][idx] = self._encode_onehot(
                         data[data_type][idx] * 255.0, expected, udc)
-            elif got > expected:
-                raise ValueError('Data type: %s, Num channels %d > Expected num channels %d' %
-                                 (data_type, got, expected))
+        return data
+
+    # -- packed label maps (``packed_labels: true``)
+    def _is_index_type(self, data_type):
+        """Static form of ``_needs_one_hot`` for a label type: an image type resized with
+        NEAREST that declares more than one channel is stored as a 1-channel index map."""
+        n = self.num_channels.get(data_type)
+        return data_type in self.image_data_types and n is not None and n > 1 and \
+            str(self.interpolators.get(data_type)).upper() == NEAREST
+
+    def get_label_layout(self):
+        """Segments ``(name, kind, out_channels, num_labels, use_dont_care)`` of ``label`` in
+        ``input_labels`` order (``ops.label``): ``'index'`` types travel as one index plane
+        under ``packed_labels``, ``'dense'`` types as their float channels. ``out_channels``
+        are the channels ``label`` really has: an index type with ``use_dont_care`` has
+        ``num_channels + 1`` (``get_label_lengths`` lists ``num_channels`` alone there)."""
+        layout = []
+        for t in self.input_labels:
+            n = self.num_channels.get(t)
+            if self._is_index_type(t):
+                udc = bool(self.use_dont_care.get(t, False))
+                layout.append((t, 'index', n + (1 if udc else 0), n, udc))
+            else:
+                if n is None:
+                    raise ValueError('packed_labels: label type %s needs num_channels' % t)
+                layout.append((t, 'dense', n, 0, False))
+        return layout
+
+    def make_packed_labels(self, data):
+        """In place of ``make_one_hot`` + stack + ``torch.cat`` under ``packed_labels``: label
+        types that ``make_one_hot`` would expand stay ONE index plane per pixel (``label_idx``
+        [T, K, H, W], uint8, or int16 above 255 labels), the other label types keep their float
+        channels (``label_dense`` [T, Cd, H, W]); the sample carries no ``label``. The trainer
+        expands the pair on the device (``ops.label.expand_packed_labels``)."""
+        from imaginaire_amd.ops.label import index_dtype
+        layout = self.get_label_layout()
+        dtype = index_dtype(layout)
+        kinds = {name: kind for name, kind, _, _, _ in layout}
+        for data_type in self.image_data_types:
+            expand = self._needs_one_hot(data_type, data[data_type][0].size(0))
+            if data_type in kinds and expand != (kinds[data_type] == 'index'):
+                raise ValueError(
+                    'packed_labels: label type %s has %d channel(s) on disk for num_channels '
+                    '%s, which does not match its static layout (%s)' % (
+                        data_type, data[data_type][0].size(0), self.num_channels[data_type],
+                        kinds[data_type]))
+            if not expand:
+                continue
+            expected = self.num_channels[data_type]
+            for idx in range(len(data[data_type])):
+                if data_type in kinds:
+                    data[data_type][idx] = self._encode_index(
+                        data[data_type][idx] * 255.0, expected, dtype)
+                else:
+                    data[data_type][idx] = self._encode_onehot(
+                        data[data_type][idx] * 255.0, expected,
+                        self.use_dont_care.get(data_type, False))
+        for t in self.image_data_types:
+            data[t] = torch.stack(data[t], dim=0)
+        planes = {t: data.pop(t) for t in self.input_labels}
+        idx = [planes[t] for t in self.input_labels if kinds[t] == 'index']
+        dense = [planes[t] for t in self.input_labels if kinds[t] == 'dense']
+        if idx:
+            data['label_idx'] = torch.cat(idx, dim=1)
+        if dense:
+            data['label_dense'] = torch.cat(dense, dim=1)
         return data
 
     # -- op language

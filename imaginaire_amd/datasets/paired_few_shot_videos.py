@@ -107,11 +107,14 @@ class Dataset(VideoDataset):
         data = self.apply_ops(data, self.post_aug_ops)
         data = self.apply_ops(data, self.full_data_post_aug_ops, full_data=True)
         data = self.to_tensor(data)
-        data = self.make_one_hot(data)
-        for t in self.image_data_types:
-            data[t] = torch.stack(data[t], dim=0)
-        if concat and self.input_labels:
-            data['label'] = torch.cat([data.pop(t) for t in self.input_labels], dim=1)
+        if self.packed_labels and concat and self.input_labels:
+            data = self.make_packed_labels(data)
+        else:
+            data = self.make_one_hot(data)
+            for t in self.image_data_types:
+                data[t] = torch.stack(data[t], dim=0)
+            if concat and self.input_labels:
+                data['label'] = torch.cat([data.pop(t) for t in self.input_labels], dim=1)
         data['is_flipped'] = is_flipped
         data['key'] = seq_keys
         data.update(kp_data)

@@ -111,11 +111,14 @@ class Dataset(BaseDataset):
         kp_data = {t + '_xy': copy.deepcopy(data[t]) for t in self.keypoint_data_types}
         data = self.apply_ops(data, self.post_aug_ops)
         data = self.to_tensor(data)
-        data = self.make_one_hot(data)
-        for t in self.image_data_types:
-            data[t] = torch.stack(data[t], dim=0)
-        if concat and self.input_labels:
-            data['label'] = torch.cat([data.pop(t) for t in self.input_labels], dim=1)
+        if self.packed_labels and concat and self.input_labels:
+            data = self.make_packed_labels(data)
+        else:
+            data = self.make_one_hot(data)
+            for t in self.image_data_types:
+                data[t] = torch.stack(data[t], dim=0)
+            if concat and self.input_labels:
+                data['label'] = torch.cat([data.pop(t) for t in self.input_labels], dim=1)
         data.update(kp_data)
         data['driving_images'] = data['videos'][0]
         data['source_images'] = data['videos'][1]

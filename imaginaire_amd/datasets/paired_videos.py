@@ -111,13 +111,20 @@ class Dataset(BaseDataset):
         data = self.apply_ops(data, self.post_aug_ops)
         data = self.apply_ops(data, self.full_data_post_aug_ops, full_data=True)
         data = self.to_tensor(data)
-        data = self.make_one_hot(data)
-        for t in self.image_data_types:
-            data[t] = torch.stack(data[t], dim=0)
-        if concat and self.input_labels:
-            data['label'] = torch.cat([data.pop(t) for t in self.input_labels], dim=1)
-            if not self.is_video_dataset:
-                data['label'] = data['label'].squeeze(0)
+        label_keys = []
+        if self.packed_labels and concat and self.input_labels:
+            data = self.make_packed_labels(data)
+            label_keys = [k for k in ('label_idx', 'label_dense') if k in data]
+        else:
+            data = self.make_one_hot(data)
+            for t in self.image_data_types:
+                data[t] = torch.stack(data[t], dim=0)
+            if concat and self.input_labels:
+                data['label'] = torch.cat([data.pop(t) for t in self.input_labels], dim=1)
+                label_keys = ['label']
+        if not self.is_video_dataset:
+            for k in label_keys:
+                data[k] = data[k].squeeze(0)
         if not self.is_video_dataset:
             for t in self.image_data_types:
                 if t in data:

@@ -114,6 +114,11 @@ class Dataset(torch.utils.data.Dataset):
         self.unprojection_points = int(getattr(syn, 'unprojection_points', 0) or 0) \
             if syn is not None else 0
         self._world = None
+        # opt-in (``packed_labels: true``): one-hot label types travel as index planes
+        self.packed_labels = bool(getattr(self.cfg_data, 'packed_labels', False))
+        if self.packed_labels:
+            from imaginaire_amd.ops.label import index_dtype
+            self._index_dtype = index_dtype(self.get_label_layout())
 
     # pixels the synthetic camera moves per frame over the world of point ids
     WORLD_SCROLL = 3
@@ -168,6 +173,57 @@ class Dataset(torch.utils.data.Dataset):
             lengths[name] = t.num_channels + (1 if getattr(t, 'use_dont_care', False) else 0)
         return lengths
 
+    def _draw_kind(self, name):
+        """How ``_frame`` draws data type ``name`` and how many channels that gives:
+        ``(kind, channels)``. The one place that decides it: ``_frame`` dispatches on the kind
+        and ``get_label_layout`` reads the kind and the channel count from here."""
+        t = self.types[name]
+        nc = t.num_channels
+        if name == 'unprojections':
+            return 'none', 0
+        if name == 'flow':
+            return 'flow', 3
+        if name in self.input_image or name.startswith('images'):
+            return 'image', nc
+        if 'densepose' in name:
+            return 'densepose', 3
+        if 'instance' in name and nc == 3:
+            return 'instance_rgb', 3
+        if getattr(t, 'interpolator', 'BILINEAR') == 'NEAREST' and nc > 1:
+            return 'one_hot', nc + (1 if getattr(t, 'use_dont_care', False) else 0)
+        if 'instance' in name:
+            return 'instance_id', 1
+        return 'map', nc
+
+    def _is_index_type(self, name):
+        """Whether ``_frame`` draws ``name`` as a one-hot Voronoi segmentation."""
+        return self._draw_kind(name)[0] == 'one_hot'
+
+    def get_label_layout(self):
+        """Segments ``(name, kind, out_channels, num_labels, use_dont_care)`` of ``label`` in
+        ``input_labels`` order (``ops.label``; the contract of ``BaseDataset``)."""
+        layout = []
+        for name in self.input_labels:
+            kind, channels = self._draw_kind(name)
+            if kind == 'none':
+                continue
+            if kind == 'one_hot':
+                n = self.types[name].num_channels
+                layout.append((name, 'index', channels, n, channels > n))
+            else:
+                layout.append((name, 'dense', channels, 0, False))
+        return layout
+
+    def _packed(self, sample, prefix, data):
+        """``label_idx`` / ``label_dense`` of a sample in place of its concatenated label."""
+        names = [n for n in self.input_labels if n in sample]
+        idx = [sample[n] for n in names if self._is_index_type(n)]
+        dense = [sample[n] for n in names if not self._is_index_type(n)]
+        if idx:
+            data[prefix + 'label_idx'] = torch.cat(idx, dim=-3)
+        if dense:
+            data[prefix + 'label_dense'] = torch.cat(dense, dim=-3)
+
     def num_inference_sequences(self):
         return max(1, self.length // max(1, self.seq_len or 1))
 
@@ -189,31 +245,35 @@ class Dataset(torch.utils.data.Dataset):
         seg = None
         for name, t in self.types.items():
             nc = t.num_channels
-            interp = getattr(t, 'interpolator', 'BILINEAR')
-            if name == 'unprojections':
+            kind = self._draw_kind(name)[0]
+            if kind == 'none':
                 continue
-            if name == 'flow':
+            if kind == 'flow':
                 # external flow (px) + occlusion mask, wc-vid2vid fork contract
                 f = smooth_field(2, h, w, gen) * 2.0
                 m = (smooth_field(1, h, w, gen) + 1) / 2
                 out[name] = torch.cat([f, m], 0)
-            elif name in self.input_image or name.startswith('images'):
+            elif kind == 'image':
                 out[name] = smooth_field(nc, h, w, gen).clamp(-1, 1)
-            elif 'densepose' in name:
+            elif kind == 'densepose':
                 # IUV map as decoded from the 8-bit PNG: U, V in [0, 1], part index I/255
                 parts = voronoi_labels(h, w, 25, gen).float() / 255.0
                 uv = (smooth_field(2, h, w, gen) + 1) / 2
                 out[name] = torch.cat([uv, parts[None]], 0)
-            elif 'instance' in name and nc == 3:
+            elif kind == 'instance_rgb':
                 ids = voronoi_labels(h, w, 4, gen).float() / 255.0
                 out[name] = ids[None].repeat(3, 1, 1)
-            elif interp == 'NEAREST' and nc > 1:
+            elif kind == 'one_hot':
                 seg = voronoi_labels(h, w, nc, gen)
+                if self.packed_labels and name in self.input_labels:
+                    # the index plane itself; the trainer expands it on the device
+                    out[name] = seg[None].to(self._index_dtype)
+                    continue
                 onehot = F.one_hot(seg, nc).permute(2, 0, 1).float()
                 if getattr(t, 'use_dont_care', False):
                     onehot = torch.cat([onehot, torch.zeros(1, h, w)], 0)
                 out[name] = onehot
-            elif 'instance' in name:
+            elif kind == 'instance_id':
                 # integer instance ids (cityscapes-style: class*1000 + k)
                 inst = voronoi_labels(h, w, 8, gen, num_sites=12)
                 base = seg if seg is not None else torch.zeros_like(inst)
@@ -238,7 +298,9 @@ class Dataset(torch.utils.data.Dataset):
             few_shot = {k: torch.stack([f[k] for f in shots]) for k in shots[0]}
         data = {}
         labels = [sample[n] for n in self.input_labels if n in sample]
-        if labels:
+        if labels and self.packed_labels:
+            self._packed(sample, '', data)
+        elif labels:
             data['label'] = torch.cat(labels, dim=-3)
         for n in self.input_image:
             if n in sample:
@@ -248,7 +310,9 @@ class Dataset(torch.utils.data.Dataset):
                 data[n] = v
         if few_shot is not None:
             shot_labels = [few_shot[n] for n in self.input_labels if n in few_shot]
-            if shot_labels:
+            if shot_labels and self.packed_labels:
+                self._packed(few_shot, 'few_shot_', data)
+            elif shot_labels:
                 data['few_shot_label'] = torch.cat(shot_labels, dim=-3)
             data['few_shot_images'] = few_shot[self.input_image[0]]
         if not self.paired and 'images' in data and 'images_b' not in data:

@@ -106,6 +106,10 @@ def get_video_activations(data_loader, key_real, key_fake, trainer=None, sample_
             elif preprocess is not None:
                 data = preprocess(data)
             data = to_device(data, device)
+            if trainer is not None:
+                # this loop copies the batch itself, not through trainer.to_device: a
+                # packed_labels batch still holds index planes here
+                data = trainer.expand_packed_labels(data)
             if trainer is None:
                 images = data[key_real][:, -1]
             else:

@@ -25,6 +25,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from imaginaire_amd.ops import _ext
+from imaginaire_amd.ops import label as label_ops
 from imaginaire_amd.ops.norm import (BiasGradHolder, _NormCfg, defer_sync_bwd, fused_norm_act,
                                      fused_norm_act_pair, prefetch_sync_stats,
                                      spade_pair_enabled, sync_active)
@@ -164,6 +165,23 @@ class LabelMapCache(object):
             return t
         key = (id(t), t.data_ptr(), tuple(size), mode, pad)
         out = cache.store.get(key) if cache is not None else None
+        packed = getattr(t, '_iamd_packed_label', None)
+        if out is None and packed is not None and mode == 'nearest' and t.dim() == 4 and \
+                _ext.use_native(t) and t.dtype in (torch.float32, torch.bfloat16) and \
+                label_ops.packed_resize_enabled() and _ext.is_dense(t):
+            # an expanded packed label: its resized (and padded) map is a function of the index
+            # planes, written by one k19 launch instead of a padded full-resolution copy plus a
+            # resize of that copy. Same values, dtype, layout and mark as the path below.
+            c = t.shape[1]
+            cl = t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
+            out = label_ops.expand_labels(
+                packed.idx, packed.dense, packed.layout, size=tuple(size),
+                pad_to=(c + 63) // 64 * 64 if pad else None, dtype=t.dtype,
+                channels_last=pad or cl)
+            if pad:
+                out = nhwc_conv.mark_zero_tail(out, c)
+            if cache is not None:
+                cache.store[key] = out
         if out is None:
             src = t
             if pad:

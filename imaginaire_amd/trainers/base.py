@@ -16,12 +16,14 @@ policies, meters, image dumps, ``speed_benchmark`` phase timers, FID-based
   also forces device syncs in ``speed_benchmark`` mode — kept, opt-in).
 """
 import contextlib
+import functools
 import os
 import time
 
 import torch
 from torch import nn
 
+from imaginaire_amd.ops.label import expand_packed_labels
 from imaginaire_amd.utils import trace
 from imaginaire_amd.utils.distributed import is_master, master_only
 from imaginaire_amd.utils.distributed import master_only_print as print
@@ -30,6 +32,24 @@ from imaginaire_amd.utils.meters import Meter, add_hparams
 from imaginaire_amd.utils.misc import requires_grad, to_device
 from imaginaire_amd.utils.model_average import calibrate_batch_norm_momentum, reset_batch_norm
 from imaginaire_amd.utils.visualization.common import save_image_grid, tensor2pilimage
+
+
+_PACKED_LABEL_KEYS = ('label_idx', 'label_dense', 'few_shot_label_idx', 'few_shot_label_dense')
+
+
+def follows_test_loader(test):
+    """For a trainer's ``test(self, data_loader, ...)``: while it runs, packed label batches
+    follow the label layout of ITS loader's dataset (``test_data`` may declare other label types
+    than ``data``); afterwards that of the training / validation loader again."""
+    @functools.wraps(test)
+    def scoped(self, data_loader, *args, **kwargs):
+        prev = getattr(self, '_test_data_loader', None)
+        self._test_data_loader = data_loader
+        try:
+            return test(self, data_loader, *args, **kwargs)
+        finally:
+            self._test_data_loader = prev
+    return scoped
 
 
 def amp_dtype_of(cfg, device):
@@ -223,8 +243,28 @@ class BaseTrainer(object):
         self.start_epoch_time = time.time()
 
     def to_device(self, data):
-        return to_device(data, self.device, non_blocking=True,
+        data = to_device(data, self.device, non_blocking=True,
                          memory_format=torch.channels_last if self.channels_last else None)
+        return self.expand_packed_labels(data)
+
+    def _label_layout(self):
+        """Label layout of the loader the current batches come from (``packed_labels``
+        datasets): the loader ``test`` is iterating, else the training / validation loader."""
+        for loader in (getattr(self, '_test_data_loader', None), self.train_data_loader,
+                       self.val_data_loader):
+            dataset = getattr(loader, 'dataset', None)
+            if hasattr(dataset, 'get_label_layout'):
+                return dataset.get_label_layout()
+        return None
+
+    def expand_packed_labels(self, data):
+        """``label_idx`` / ``label_dense`` of a ``packed_labels`` batch -> the ``label`` the
+        unpacked loader delivers (``ops.label``: k19 on the GPU). Every loader batch passes
+        here through ``to_device``; batches without packed keys are returned as they are."""
+        if isinstance(data, dict) and any(k in data for k in _PACKED_LABEL_KEYS):
+            data = expand_packed_labels(data, self._label_layout(),
+                                        channels_last=self.channels_last)
+        return data
 
     def start_of_iteration(self, data, current_iteration):
         data = self._start_of_iteration(data, current_iteration)
@@ -451,6 +491,7 @@ class BaseTrainer(object):
     def dis_forward(self, data):
         raise NotImplementedError
 
+    @follows_test_loader
     def test(self, data_loader, output_dir, inference_args):
         if self.cfg.trainer.model_average:
             net_G = self.net_G.module.averaged_model

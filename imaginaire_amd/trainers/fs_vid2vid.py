@@ -10,6 +10,7 @@ import torch
 from imaginaire_amd.model_utils.fs_vid2vid import (concat_frames, get_fg_mask,
                                                    pre_process_densepose, random_roll)
 from imaginaire_amd.model_utils.pix2pixHD import get_optimizer_with_params
+from imaginaire_amd.trainers.base import follows_test_loader
 from imaginaire_amd.trainers.vid2vid import Trainer as Vid2VidTrainer
 from imaginaire_amd.trainers.vid2vid import _imwrite, _save_video
 from imaginaire_amd.utils.distributed import is_master
@@ -23,6 +24,7 @@ class Trainer(Vid2VidTrainer):
         if hasattr(data_cfg, 'for_pose_dataset') and \
                 'pose_maps-densepose' in data_cfg.input_labels:
             pose_cfg = data_cfg.for_pose_dataset
+            data = self.expand_packed_labels(data)  # read here, before the copy
             data['label'] = pre_process_densepose(pose_cfg, data['label'], self.is_inference)
             data['few_shot_label'] = pre_process_densepose(pose_cfg, data['few_shot_label'],
                                                            self.is_inference)
@@ -59,6 +61,7 @@ class Trainer(Vid2VidTrainer):
                 net_G_output['fake_raw_images'] = net_G_output['fake_raw_images'] * fg_mask
         return data, net_G_output
 
+    @follows_test_loader
     def test(self, test_data_loader, root_output_dir, inference_args):
         self.reset()
         test_data_loader.dataset.set_sequence_length(0)

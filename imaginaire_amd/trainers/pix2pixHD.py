@@ -8,6 +8,7 @@ import torch
 from imaginaire_amd.evaluation import compute_fid
 from imaginaire_amd.losses import FeatureMatchingLoss, GANLoss, PerceptualLoss
 from imaginaire_amd.model_utils.pix2pixHD import cluster_features, get_edges
+from imaginaire_amd.ops.label import cast_label
 from imaginaire_amd.trainers.spade import Trainer as SPADETrainer
 from imaginaire_amd.utils.distributed import master_only_print as print
 
@@ -37,7 +38,7 @@ class Trainer(SPADETrainer):
             # stays fp32 for the feature encoder's instance pooling)
             for key in ('label', 'images'):
                 if torch.is_tensor(data.get(key)) and data[key].is_floating_point():
-                    data[key] = data[key].to(self.amp_dtype)
+                    data[key] = cast_label(data[key], self.amp_dtype)
         return data
 
     def gen_forward(self, data):

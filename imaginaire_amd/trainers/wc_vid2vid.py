@@ -16,6 +16,7 @@ from imaginaire_amd.generators.wc_vid2vid import guidance_key
 from imaginaire_amd.losses import MaskedL1Loss
 from imaginaire_amd.model_utils.fs_vid2vid import concat_frames
 from imaginaire_amd.model_utils.wc_vid2vid.render import unprojections_to_rows
+from imaginaire_amd.trainers.base import follows_test_loader
 from imaginaire_amd.trainers.vid2vid import Trainer as Vid2VidTrainer
 from imaginaire_amd.trainers.vid2vid import _imwrite, _save_video
 from imaginaire_amd.utils.distributed import is_master
@@ -93,6 +94,7 @@ class Trainer(Vid2VidTrainer):
         os.makedirs(output_dir + '/fake', exist_ok=True)
         return output_dir, seq_name
 
+    @follows_test_loader
     def test(self, test_data_loader, root_output_dir, inference_args):
         loader = test_data_loader
         for sequence_idx in range(loader.dataset.num_inference_sequences()):
